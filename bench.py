@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark: tri-modal Bayesian MC training step (BASELINE.json configs[1]) on MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...     (driver, one rank per GPU, RCCL)
 
 A step = one reference training batch (train/multimodal.py:104-146) of synthetic triplets
@@ -10,8 +10,12 @@ cross-entropy, backward, RCCL gradient all-reduce (N>1), NaN/Inf guard, Adam ste
 Workload per GPU: B=64 triplets, optical 3x224x224 ~N(0,1), bathy 3x256x256 ~U[0,1) with
 channel 2 = 0, SSS 1x256x256 ~U[0,1), 7 classes, fp32 (weak scaling: 64 per GPU).
 
-Also reported: the same step with bf16 trunks (configs[2]'s per-GPU slice, `bf16_train`),
-MC inference (configs[3]: 100 passes over 256 triplets, MC-sharded across ranks, under
+A plain run sets up, warms up, times the K steps, writes the last timed step's results with
+--dump-outputs, and prints the result line.  Every other leg runs only with --full (their
+fields of the line are null without it).
+
+With --full also reported: the same step with bf16 trunks (configs[2]'s per-GPU slice,
+`bf16_train`), MC inference (configs[3]: 100 passes over 256 triplets, MC-sharded across ranks, under
 torch.autocast as the reference predictor runs it -> f16 trunks), the roofline of the dominant
 kernel family (implicit-GEMM conv fwd/dgrad/wgrad, HIP-event timed inside this run), and the
 reference-semantics CPU path (oracle/, torch-CPU fp32, sequential MC loop) timed on a bounded
@@ -298,6 +302,26 @@ def roofline_step(step_fn, peak=FP32_MFMA_PEAK_TF, traffic="fp32", suffix="",
     }
 
 
+def dump_outputs(out_dir, result, model, sample=1 << 20):
+    """What a caller of the timed step holds after it, as float32 <name>.npy files: the dict
+    mc_train_step returned (losses, mean logits, predictions, skip flags) and the parameters
+    the step updated.  The parameters (~147 M values) are sampled at `sample` fixed positions
+    of their concatenation (seeded, sorted), the same positions in every run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    for k, v in (result or {}).items():
+        arrays[k] = torch.as_tensor(v).detach().to("cpu", torch.float32).numpy()
+    flat = torch.cat([p.detach().reshape(-1).float() for p in model.parameters()])
+    if flat.numel() > sample:
+        g = torch.Generator(device="cpu").manual_seed(20240229)
+        idx = torch.randint(0, flat.numel(), (sample,), generator=g).sort().values
+        flat = flat[idx.to(flat.device)]
+    arrays["params_sample"] = flat.cpu().numpy()
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` without torchrun: N child processes of this script, rank r on
     GPU r (torch.distributed env rendezvous on 127.0.0.1), started before this parent
@@ -342,6 +366,13 @@ def main():
                          "Without torchrun, N > 1 starts N rank processes itself")
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned and a "
+                         "fixed seeded sample of the updated parameters as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: roofline, exact-f32 and bf16 "
+                         "steps, the configs[4] / configs[0] sweeps, MC inference and the CPU "
+                         "baseline (each still has its own --no-* switch)")
     ap.add_argument("--batch", type=int, default=64, help="triplets per GPU")
     ap.add_argument("--num-mc", type=int, default=5)
     ap.add_argument("--optical", type=int, default=224)
@@ -382,6 +413,12 @@ def main():
                     help="torch.distributed backend for world > 1 (nccl = RCCL over xGMI; gloo "
                          "rehearses the multi-rank harness, e.g. two ranks on one GPU)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.no_roofline = args.no_bf16 = args.no_sweep = True
+        args.no_infer = args.no_infer_sweep = args.no_cpu_baseline = True
+        args.exact_steps = 0
 
     # --gpus N is honoured or refused, never silently measured on one GPU: without a launcher
     # (WORLD_SIZE unset) N > 1 ranks are started here, before this process touches the GPU;
@@ -456,7 +493,7 @@ def main():
     c0 = (model.n_buckets, model.n_overlapped, model.elems_reduced) if world > 1 else None
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step()
+        last = step()
         if rank == 0 and args.steps > 3:
             print(f"[bench] step {i + 1}/{args.steps}", file=sys.stderr, flush=True)
     torch.cuda.synchronize()
@@ -486,6 +523,8 @@ def main():
                         "slices all-reduced during the backward, the remaining buckets, the "
                         "1/world scale), HIP events over the timed steps"}
     triplets_s = args.batch * world * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, model)
     from mauv import ops
     f32_math = ops.f32_math()
     roof = None
@@ -512,7 +551,8 @@ def main():
         return t
 
     exact = None
-    progress("roofline step done")
+    if roof is not None:
+        progress("roofline step done")
     if args.dtype == "fp32" and args.exact_steps > 0 and f32_math != "exact":
         progress("exact-f32 leg")
         # the same step with every fp32 product on v_mfma_f32_32x32x2_f32 (reference point)

@@ -26,7 +26,7 @@ def _free_port():
 def test_bench_world2_gloo_one_gpu():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo",
+           os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--backend", "gloo",
            "--steps", "2", "--warmup", "1", "--batch", "4", "--num-mc", "2",
            "--optical", "64", "--sonar", "64", "--sweep-batch", "2", "--leg-steps", "1",
            "--infer-batch", "8", "--infer-mc", "6", "--infer-sweep-batch", "4",
@@ -78,7 +78,7 @@ def test_bench_world4_gloo_uneven_mc_shards():
     """four ranks on one GPU, 10 MC samples over 4 ranks (3, 3, 2, 2)."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "4", "--backend", "gloo",
+           os.path.join(ROOT, "bench.py"), "--full", "--gpus", "4", "--backend", "gloo",
            "--steps", "2", "--warmup", "1", "--batch", "2", "--num-mc", "2",
            "--optical", "64", "--sonar", "64", "--infer-batch", "4", "--infer-mc", "10",
            "--no-sweep", "--no-infer-sweep", "--no-infer-fp32", "--exact-steps", "0",

@@ -9,13 +9,15 @@ SUBpackage such as `Multimodal_AUV.inference.inference_data` (`main.py:14`,
 `Examples/Example_training_from_scratch.py:17`).  The reference's documented top-level API
 (`__init__.py:5-10`, used at `README - pypi.md:324,402,515,594`) must re-export.
 
-Third-party modules the reference imports that are absent from this image (torchvision,
-tensorboard, pynvml, skimage, cv2, rasterio, pyproj, utm, exiftool) get name-only shims, the
-way `tests/golden/make_golden.py:48-78` installs them; nothing of theirs runs at import time.
-Runs in a subprocess so the shims and the reference path never leak into other tests.  Needs
-`/root/reference` (this container only; the GPU box has no reference).
+The reference package is not part of this repository, so the test builds a stand-in for it in
+a temporary directory from `tests/golden/reference_imports.json` (recorded from the reference
+by `tests/golden/make_reference_imports.py`: per file, the `Multimodal_AUV.*` modules and
+names it imports): the same package layout and file names, each file holding exactly the
+reference file's `Multimodal_AUV.*` import statements plus a placeholder for every name another
+file imports from it.  What is under test is the drop-in's side: which file each module name
+resolves to, and that the drop-in exports every name the reference's files import from it.
+Runs in a subprocess so the stand-in never leaks into other tests.
 """
-import ast
 import json
 import os
 import subprocess
@@ -26,72 +28,49 @@ import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG_ROOT = os.path.join(REPO, "multimodal-auv_amd")
-REF_PKG = "/root/reference/src/Multimodal_AUV"
-
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF_PKG),
-                                reason="reference checkout not present")
-
-ENTRY_FILES = ["main.py", "cli.py", "functions/functions.py"]
-
-
-def _entry_files():
-    ex = os.path.join(REF_PKG, "Examples")
-    return ENTRY_FILES + sorted("Examples/" + f for f in os.listdir(ex)
-                                if f.endswith(".py") and f != "__init__.py")
-
-
-def _all_files():
-    for d, _, fs in os.walk(REF_PKG):
-        for f in fs:
-            if f.endswith(".py"):
-                yield os.path.relpath(os.path.join(d, f), REF_PKG)
+with open(os.path.join(REPO, "tests", "golden", "reference_imports.json")) as _f:
+    RECORD = json.load(_f)
 
 
 def _imported_modules():
-    """Every `Multimodal_AUV.*` module any reference file imports (parsed, not executed)."""
-    mods = set()
-    for rel in _all_files():
-        tree = ast.parse(open(os.path.join(REF_PKG, rel), encoding="utf-8-sig").read())
-        for node in ast.walk(tree):
-            if isinstance(node, ast.ImportFrom) and node.module and \
-                    node.module.startswith("Multimodal_AUV."):
-                mods.add(node.module)
-            elif isinstance(node, ast.Import):
-                mods.update(a.name for a in node.names if a.name.startswith("Multimodal_AUV."))
-    return sorted(mods)
+    """Every `Multimodal_AUV.*` module any reference file imports (recorded, not executed)."""
+    return sorted({row[0] for rows in RECORD["files"].values() for row in rows})
+
+
+def _module_file(module):
+    return module.split(".", 1)[1].replace(".", "/") + ".py"
+
+
+@pytest.fixture(scope="module")
+def ref_pkg(tmp_path_factory):
+    """The stand-in reference package: <tmp>/src/Multimodal_AUV."""
+    root = tmp_path_factory.mktemp("reference") / "src" / "Multimodal_AUV"
+    wanted = {}                      # file -> names other files import from it
+    for rows in RECORD["files"].values():
+        for module, names, _ in rows:
+            wanted.setdefault(_module_file(module), set()).update(names)
+    wanted.setdefault("functions/functions.py", set()).update(RECORD["api"])
+    for pkg in RECORD["packages"]:
+        (root / pkg).mkdir(parents=True, exist_ok=True)
+        (root / pkg / "__init__.py").write_text("")
+    for rel in sorted(set(wanted) | set(RECORD["files"])):
+        top, deferred = [], []
+        for module, names, inside in RECORD["files"].get(rel, []):
+            line = f"from {module} import {', '.join(names)}" if names else f"import {module}"
+            (deferred if inside else top).append(line)
+        src = top + ["", "def _deferred_imports():"] + ["    " + ln for ln in deferred or ["pass"]]
+        for name in sorted(wanted.get(rel, ())):
+            src += ["", f"def {name}(*args, **kwargs):",
+                    "    raise NotImplementedError('stand-in for the reference')"]
+        (root / rel).write_text("\n".join(src) + "\n")
+    return str(root)
 
 
 _SCRIPT = textwrap.dedent(r'''
-    import importlib, importlib.abc, importlib.machinery, importlib.util, json, os, sys, types
+    import importlib, importlib.util, json, os, sys
     sys.path[:0] = [PKG_ROOT, REPO]
     os.environ["MAUV_REFERENCE_PKG"] = REF_PKG
     os.environ.setdefault("MPLBACKEND", "Agg")
-
-    ABSENT = ["torchvision", "tensorboard", "pynvml", "skimage", "cv2", "rasterio", "pyproj",
-              "utm", "exiftool"]
-    ROOTS = {r for r in ABSENT if importlib.util.find_spec(r) is None}
-
-    class _Dummy:
-        def __init__(self, *a, **k): pass
-        def __call__(self, *a, **k): return _Dummy()
-        def __getattr__(self, k): return _Dummy()
-
-    class _NameOnly(types.ModuleType):
-        def __getattr__(self, k):
-            if k.startswith("__"):
-                raise AttributeError(k)
-            return _Dummy
-
-    class _Finder(importlib.abc.MetaPathFinder, importlib.abc.Loader):
-        def find_spec(self, name, path=None, target=None):
-            if name.split(".")[0] in ROOTS or name == "torch.utils.tensorboard":
-                return importlib.machinery.ModuleSpec(name, self, is_package=True)
-            return None
-        def create_module(self, spec):
-            m = _NameOnly(spec.name); m.__path__ = []; return m
-        def exec_module(self, m): pass
-
-    sys.meta_path.insert(0, _Finder())
 
     out = {"modules": {}, "api": {}, "entry": {}}
     for name in MODULES:
@@ -118,28 +97,29 @@ _SCRIPT = textwrap.dedent(r'''
 ''')
 
 
-def _run(modules, entries):
-    code = (f"PKG_ROOT={PKG_ROOT!r}\nREPO={REPO!r}\nREF_PKG={REF_PKG!r}\n"
+def _run(modules, entries, ref_pkg, cwd):
+    code = (f"PKG_ROOT={PKG_ROOT!r}\nREPO={REPO!r}\nREF_PKG={ref_pkg!r}\n"
             f"MODULES={modules!r}\nENTRIES={entries!r}\n" + _SCRIPT)
     env = dict(os.environ)
     env.pop("MAUV_REFERENCE_PKG", None)
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True,
-                       env=env, timeout=600, cwd="/tmp")
+                       env=env, timeout=600, cwd=cwd)
     assert r.returncode == 0, r.stderr[-4000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1]
     return json.loads(line[len("RESULT "):])
 
 
-def test_reference_entry_points_import_on_dropin():
+def test_reference_entry_points_import_on_dropin(ref_pkg, tmp_path):
     mods = _imported_modules()
     assert "Multimodal_AUV.inference.inference_data" in mods
     assert len(mods) >= 19, mods
     entries = [("main.py", "Multimodal_AUV.main"),
                ("Examples/Example_training_from_scratch.py",
                 "Multimodal_AUV.Examples.Example_training_from_scratch")]
-    res = _run(mods, entries)
+    res = _run(mods, entries, ref_pkg, str(tmp_path))
+    assert set(res["modules"]) == set(mods)
     dropin = os.path.realpath(os.path.join(PKG_ROOT, "Multimodal_AUV"))
-    ref = os.path.realpath(REF_PKG)
+    ref = os.path.realpath(ref_pkg)
     on_path = {"Multimodal_AUV.models.model_utils", "Multimodal_AUV.utils.device",
                "Multimodal_AUV.train.loop_utils", "Multimodal_AUV.train.checkpointing",
                "Multimodal_AUV.inference.predictors"}
@@ -161,7 +141,7 @@ def test_reference_entry_points_import_on_dropin():
             "Multimodal_AUV.inference.inference_data", (rel, names)
 
 
-def test_run_api_without_reference_is_actionable():
+def test_run_api_without_reference_is_actionable(tmp_path):
     code = (f"import sys; sys.path[:0]=[{PKG_ROOT!r}, {REPO!r}]\n"
             "import Multimodal_AUV\n"
             "try:\n    from Multimodal_AUV import run_auv_inference\n"
@@ -169,6 +149,6 @@ def test_run_api_without_reference_is_actionable():
     env = dict(os.environ)
     env.pop("MAUV_REFERENCE_PKG", None)
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env,
-                       timeout=300, cwd="/tmp")
+                       timeout=300, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-2000:]
     assert "MAUV_REFERENCE_PKG" in r.stdout

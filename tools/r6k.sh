@@ -7,7 +7,7 @@ timeout -k 10 900 python -u -m pytest -x -v -rP --timeout 300 --timeout-method t
   tests/test_centre16_gpu.py tests/test_fold_gpu.py tests/test_big16_gpu.py tests/test_expand16_gpu.py \
   tests/test_haloc16_gpu.py tests/test_halo16_gpu.py tests/test_kernels16_gpu.py \
   > $O/r6k_tests.log 2>&1; r=$?; tail -2 $O/r6k_tests.log; [ $r -eq 0 ] || { grep -E "FAILED|Error" $O/r6k_tests.log | head -20; exit 1; }
-C="--steps 1 --warmup 0 --no-cpu-baseline --exact-steps 0 --no-roofline --no-sweep --no-infer-sweep --no-bf16 --no-infer-fp32"
+C="--full --steps 1 --warmup 0 --no-cpu-baseline --exact-steps 0 --no-roofline --no-sweep --no-infer-sweep --no-bf16 --no-infer-fp32"
 MAUV_LIB=$PWD/abtmp/libmauv_head.so MAUV_CENTRE_Y=0 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/hd0 -o run -- python3 bench.py $C > $O/hd0.log 2>&1 || exit 1
 MAUV_CENTRE_Y=0 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/nw0 -o run -- python3 bench.py $C > $O/nw0.log 2>&1 || exit 1
 MAUV_CENTRE_Y=1 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/nw1 -o run -- python3 bench.py $C > $O/nw1.log 2>&1 || exit 1
