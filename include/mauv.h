@@ -202,7 +202,7 @@ int mauv_reparam_sample(const float* mu, const float* rho, const float* eps,
 /* Backward of the above: dmu += sum_g dW_g; drho += sum_g dW_g * eps_g' * sigmoid(rho),
  * g' = g (fixed_sample < 0) or the sample `fixed_sample` for every g (bayesian-torch 0.5.0
  * semantics: its eps buffer is overwritten in place by later MC forwards while autograd
- * still references it).  dw element (s, g, i) at dw[s*dw_sstride + g*dw_gstride + i], i in
+ * still references it; 0 <= fixed_sample < sample0 is an argument error).  dw element (s, g, i) at dw[s*dw_sstride + g*dw_gstride + i], i in
  * KRSC order with dw_cin (>= Cin; the 16-bit stems' padded channel count) channels. */
 int mauv_reparam_bwd(const float* dw, int splits, long long dw_gstride, long long dw_sstride,
                      const float* mu, const float* rho, const float* eps,

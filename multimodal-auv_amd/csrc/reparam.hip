@@ -514,6 +514,12 @@ MAUV_API int mauv_reparam_bwd(const float* dw, int splits, long long dw_gstride,
   const long long gs = dw_gstride ? dw_gstride : (long long)Cout * RS * dw_cin;
   const long long ss = dw_sstride ? dw_sstride : gs * G;
   if (RS > 49) { set_error("reparam_bwd: R*S > 49"); return kErrArg; }
+  // the kernels take the mode from fixed_sample - sample0 (>= 0: one epsilon for every g); a
+  // fixed sample before this forward's first one would run exact mode with fixed-mode sizing
+  if (fixed_sample >= 0 && (unsigned long long)fixed_sample < sample0) {
+    set_error("reparam_bwd: 0 <= fixed_sample < sample0");
+    return kErrArg;
+  }
   (void)nq;
   const int nt = (fixed_sample >= 0 ? G : 1) * splits;
   const int v4 = (mauv::g_route.reparam_kernels >> 1) & 1;

@@ -34,16 +34,29 @@ def philox4x32_10(q, sample, layer, seed):
     return np.stack([c0, c1, c2, c3], axis=1).astype(np.uint32)
 
 
-def normal4(raw):
-    """Box-Muller on Philox words exactly as mauv_common.h::normal4 (in float64)."""
-    u = (raw.astype(np.float64) + 0.5) * 2.0 ** -32
+def uniforms32(raw):
+    """The uniforms as mauv_common.h::normal4 forms them: ``((float)r + 0.5f) * 2^-32`` with
+    every step rounded to fp32 (the conversion rounds r to 24 bits, the + 0.5 is absorbed above
+    2^24, and a word >= 2^32 - 128 rounds up to u = 1), returned as float64."""
+    f = raw.astype(np.float32)
+    f = (f + np.float32(0.5)).astype(np.float32)
+    return (f * np.float32(2.0 ** -32)).astype(np.float32).astype(np.float64)
+
+
+def normal4(raw, u32=False):
+    """Box-Muller on Philox words as mauv_common.h::normal4.  u32=False: uniforms and transform in
+    float64 (the ideal generator); u32=True: the kernel's fp32-rounded uniforms, then log, sqrt,
+    cos and sin in float64 — what the kernel computes up to the error of its fp32 libm calls (the
+    two differ by up to ~1e-5 in a normal: the fp32 uniform moves by up to 2^-25 relative)."""
+    u = uniforms32(raw) if u32 else (raw.astype(np.float64) + 0.5) * 2.0 ** -32
     m0 = np.sqrt(-2.0 * np.log(u[:, 0]))
     m1 = np.sqrt(-2.0 * np.log(u[:, 2]))
     return np.stack([m0 * np.cos(2 * np.pi * u[:, 1]), m0 * np.sin(2 * np.pi * u[:, 1]),
                      m1 * np.cos(2 * np.pi * u[:, 3]), m1 * np.sin(2 * np.pi * u[:, 3])], axis=1)
 
 
-def eps_for_layer(numel, seed, sample, layer):
+def eps_for_layer(numel, seed, sample, layer, u32=False):
     """The epsilon tensor (parameter order) the GPU draws for one layer / MC sample."""
     nq = (numel + 3) // 4
-    return normal4(philox4x32_10(np.arange(nq, dtype=np.uint64), sample, layer, seed)).reshape(-1)[:numel]
+    raw = philox4x32_10(np.arange(nq, dtype=np.uint64), sample, layer, seed)
+    return normal4(raw, u32=u32).reshape(-1)[:numel]

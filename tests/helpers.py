@@ -61,6 +61,84 @@ class EpsBridge:
         return prov
 
 
+# mauv_common.h::normal4 against oracle.philox_ref.normal4(u32=True): max |gpu - ref| /
+# max(|ref|, 2^-10) in units of 2^-24, measured once on an MI355X over the quads of
+# tests/test_philox_stream_gpu.py::test_philox_raw_counter_edges (the error of the kernel's fp32
+# logf / sqrtf / sincospif), and the asserted bar: 4x that, for libm differences between ROCm
+# releases
+NORMAL_MEASURED = 3.93    # worst of 2^18 quads at (seed 0x123456789ABC, sample 77, layer 6)
+NORMAL_BAR = 4 * NORMAL_MEASURED   # 15.72: 5.6e-6 absolute at |eps| = 6
+
+
+def normal_err_units(got, ref_raw):
+    """max |got - ref| / max(|ref|, 2^-10) in units of 2^-24 of GPU normals [nq * 4] against the
+    fp32-uniform restatement of the same Philox words (the figure NORMAL_BAR bounds)."""
+    import numpy as np
+    from oracle.philox_ref import normal4
+    ref = normal4(ref_raw, u32=True)
+    got = np.asarray(got, dtype=np.float64).reshape(-1, 4)
+    assert np.isfinite(got).all()
+    return float((np.abs(got - ref) / np.maximum(np.abs(ref), 2.0 ** -10)).max() * 2.0 ** 24)
+
+
+def _bayes_tensors(mauv_model):
+    """[(module name, module, eps name, numel, bias?)] of every Bayesian tensor of a mauv model,
+    in module order: the (layer, tensor) pairs the engine draws an epsilon for."""
+    from mauv.layers import is_bayesian
+    out = []
+    for n, mod in mauv_model.named_modules():
+        if not is_bayesian(mod):
+            continue
+        w = "kernel" if hasattr(mod, "mu_kernel") else "weight"
+        out.append((n, mod, w, getattr(mod, "mu_" + w).numel(), False))
+        if mod.mu_bias is not None:
+            out.append((n, mod, "bias", mod.mu_bias.numel(), True))
+    return out
+
+
+def philox_store(mauv_model, seed, s0, passes, u32=True):
+    """The epsilons the free-running engine draws for MC samples s0 .. s0+passes-1, restated on
+    the CPU (oracle.philox_ref.eps_for_layer keyed by the engine's own layer ids) in the format
+    EpsBridge.collect produces — {(module name, "kernel"|"weight"|"bias"): [eps of pass 0, 1,
+    ...]}, fp32 like the recorded draws — so oracle_replay / oracle64 replay the production
+    stream."""
+    from mauv.engine import root_state
+    from oracle.philox_ref import eps_for_layer
+    st = root_state(mauv_model)
+    store = {}
+    for n, mod, name, numel, bias in _bayes_tensors(mauv_model):
+        lid = st.layer_id(mod, bias)
+        store[(n, name)] = [torch.from_numpy(eps_for_layer(numel, seed, s0 + g, lid, u32=u32)).float()
+                            for g in range(passes)]
+    return store
+
+
+class PhiloxRawProvider:
+    """eps_provider that serves each layer's [G, numel] from ops.philox_raw(seed, s0 + g,
+    layer id, quads): the normals the sampling and backward kernels themselves draw, fed through
+    the explicit-epsilon path.  A layer asked in more than one engine call (MC chunks, sequential
+    forwards) gets the next G sample indices each time, as EpsBridge.sequential hands out the
+    recorded passes."""
+
+    def __init__(self, model, seed, s0):
+        from mauv.engine import root_state
+        self.st, self.seed, self.s0 = root_state(model), seed, s0
+        self.numel = {(id(mod), name): (numel, bias)
+                      for _, mod, name, numel, bias in _bayes_tensors(model)}
+        self.used = {}
+
+    def __call__(self, module, name, G):
+        from mauv import ops
+        key = (id(module), name)
+        numel, bias = self.numel[key]
+        i = self.used.get(key, 0)
+        self.used[key] = i + G
+        lid = self.st.layer_id(module, bias)
+        rows = [ops.philox_raw(self.seed, self.s0 + i + g, lid, (numel + 3) // 4)[1][:numel]
+                for g in range(G)]
+        return torch.stack(rows).contiguous()
+
+
 def oracle64(o, store, fn):
     """Run ``fn(o64)`` on a float64 copy of the oracle, replaying the recorded epsilons
     (``store`` from EpsBridge.collect) in the same per-layer order -> the 'truth' used to

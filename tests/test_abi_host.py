@@ -143,6 +143,42 @@ def test_philox_known_answers():
     assert [hex(v) for v in r] == ["0x408f276d", "0x41c83b0e", "0xa20bc7c6", "0x6d5451fd"]
 
 
+def test_philox_restatement_fp32_uniforms():
+    """oracle.philox_ref with u32=True rounds the uniforms as mauv_common.h::normal4 does
+    (``((float)r + 0.5f) * 2^-32`` in fp32) before a float64 Box-Muller.  Over 2^20 quads it stays
+    within 2e-5 of the float64-uniform normals (a uniform moves by <= 2^-25 relative, i.e. a
+    normal by <= 2^-25 / |eps| through the log and 2 pi 2^-25 |eps| through the angle) without
+    being identical to them; every normal is finite and within the Box-Muller bound of the
+    smallest uniform 2^-33; a layer whose numel is no multiple of 4 gets the leading elements of
+    its last quad."""
+    import math
+    from oracle.philox_ref import philox4x32_10, normal4, uniforms32, eps_for_layer
+    seed = 0x1234_5678_9ABC
+    raw = philox4x32_10(np.arange(1 << 20, dtype=np.uint64), 77, 6, seed)
+    n64, n32 = normal4(raw), normal4(raw, u32=True)
+    d = np.abs(n64 - n32).max()
+    assert 0 < d <= 2e-5, d
+    bound = math.sqrt(-2.0 * math.log(2.0 ** -33))
+    for n in (n64, n32):
+        assert n.shape == (1 << 20, 4) and np.isfinite(n).all()
+        assert np.abs(n).max() <= bound
+    # the fp32 rounding at the ends of the word range: u in [2^-33, 1], never 0
+    edge = np.array([[0, 1, 2 ** 24 + 1, 2 ** 32 - 129], [2 ** 32 - 128, 2 ** 32 - 1, 3, 2 ** 31]],
+                    dtype=np.uint32)
+    u = uniforms32(edge)
+    assert u[0, 0] == 2.0 ** -33 and u[0, 1] == 1.5 * 2.0 ** -32 and u[0, 2] == 2.0 ** -8
+    assert u[0, 3] == 1 - 2.0 ** -24 and u[1, 0] == 1.0 and u[1, 1] == 1.0
+    ne = normal4(edge, u32=True)
+    assert np.isfinite(ne).all() and np.abs(ne).max() <= bound
+    for u32 in (False, True):
+        e8 = eps_for_layer(8, seed, 2 ** 32 + 5, 347, u32=u32)
+        e7 = eps_for_layer(7, seed, 2 ** 32 + 5, 347, u32=u32)
+        assert e7.shape == (7,) and e8.shape == (8,) and np.array_equal(e7, e8[:7])
+        assert np.isfinite(e8).all() and np.abs(e8).max() <= bound
+    assert np.array_equal(eps_for_layer(8, seed, 77, 6, u32=True), n32[:2].reshape(-1))
+    assert np.array_equal(eps_for_layer(8, seed, 77, 6), n64[:2].reshape(-1))
+
+
 def test_kl_table_packing():
     from mauv.kl import KLTable
     from mauv.layers import LinearReparameterization
