@@ -426,7 +426,27 @@ int mauv_attn_out_bwd(const float* dcomb, int comb_ld, int comb_off, const float
 /* bias gradients of the linear layers */
 int mauv_colsum(const float* dy, int G, int rows, int N, float* out, int accumulate,
                 hipStream_t stream);
-/* train/multimodal.py:121 (mean over MC), :127 (CrossEntropyLoss), :151 (argmax) */
+/* The MC head: logits [G][B][C] fp32 (G MC samples), 1 <= C <= 4096 classes (the bound of
+ * mauv_confusion_update); more is -1 with the bound in mauv_last_error().  B == 0 or G == 0
+ * launches nothing and returns 0.  C <= 32 runs one thread per item (the reference's C = 7);
+ * 33 <= C <= 4096 runs the many-class kernels: lanes along the class axis (coalesced rows), a
+ * wave or a block per item, cross-lane max / sum / argmax, no scratch memory and no atomics, so
+ * every output is bit-reproducible from run to run.  Rules both families share: argmax is the
+ * first strict maximum (ties -> the lowest class index), a NaN never wins and an all-NaN row
+ * gives class 0; non-finite logits propagate into the loss and the sums; eps_h is added inside
+ * the log per sample, eps_pred in mauv_mc_finalize.
+ * Labels (int64 [B]), many-class kernels: -100 (torch's ignore_index) leaves the item out of the
+ * loss sum and of its divisor and zeroes the item's dlogits rows (no counted item: NaN loss, as
+ * torch); any other label outside [0, C) makes the loss and the item's dlogits NaN (the step
+ * gate then skips the batch, as the reference skips a non-finite loss); no label indexes memory
+ * unchecked.  The C <= 32 kernels index mean[b][label] directly: labels must be in [0, C).
+ * Sum order: the mean is the sum over g = 0..G-1 (fp32 for C <= 32; float64, rounded once, for
+ * C > 32) over G; the many-class loss is a float64 sum over the items in a fixed order by one
+ * block; sums[b][*] add the samples g = 0..G-1 in float64 in that order — with accumulate != 0
+ * the C > 32 kernels continue from the stored value, so a call sequence over chunks of the
+ * samples gives the bits of one call (C <= 32: the chunk's own sum is added to the stored one).
+ * train/multimodal.py:121 (mean over MC), :127 (CrossEntropyLoss), :151 (argmax); labels, loss
+ * and pred nullable */
 int mauv_mc_mean_ce(const float* logits, const long long* labels, int G, int B, int C,
                     float* mean, float* loss, long long* pred, hipStream_t stream);
 int mauv_mc_mean_bwd(const float* dmean, const float* gloss, const float* mean,

@@ -690,7 +690,16 @@ def colsum(dy, G, rows, N, out, accumulate=False):
     check(lib.mauv_colsum(_p(dy), G, rows, N, _p(out), int(accumulate), stream()), "colsum")
 
 
+MC_MAX_CLASSES = 4096   # include/mauv.h: the MC head's (and the confusion matrix's) class bound
+
+
+def _mc_classes(C):
+    if not 1 <= C <= MC_MAX_CLASSES:
+        raise ValueError(f"the MC head takes 1 <= C <= {MC_MAX_CLASSES} classes, got C={C}")
+
+
 def mc_mean_ce(logits, labels, G, B, C, mean, loss, pred=None):
+    _mc_classes(C)
     _dev(torch.float32, logits, mean, loss)
     _dev(torch.int64, labels, pred)
     check(lib.mauv_mc_mean_ce(_p(logits), _p(labels), G, B, C, _p(mean), _p(loss), _p(pred),
@@ -698,6 +707,7 @@ def mc_mean_ce(logits, labels, G, B, C, mean, loss, pred=None):
 
 
 def mc_mean_bwd(dmean, gloss, mean, labels, G, B, C, dlogits):
+    _mc_classes(C)
     _dev(torch.float32, dmean, gloss, mean, dlogits)
     _dev(torch.int64, labels)
     check(lib.mauv_mc_mean_bwd(_p(dmean), _p(gloss), _p(mean), _p(labels), G, B, C,
@@ -705,6 +715,7 @@ def mc_mean_bwd(dmean, gloss, mean, labels, G, B, C, dlogits):
 
 
 def mc_stats(logits, G, B, C, eps_h, sums, accumulate=False):
+    _mc_classes(C)
     _dev(torch.float32, logits)
     _dev(torch.float64, sums)
     check(lib.mauv_mc_stats(_p(logits), G, B, C, eps_h, _p(sums), int(accumulate), stream()),
@@ -713,6 +724,7 @@ def mc_stats(logits, G, B, C, eps_h, sums, accumulate=False):
 
 def mc_finalize(sums, N, B, C, eps_pred, mean_prob=None, var_unc=None, alea=None,
                 pred_entropy=None, pred=None):
+    _mc_classes(C)
     _dev(torch.float64, sums)
     _dev(torch.float32, mean_prob, var_unc, alea, pred_entropy)
     _dev(torch.int64, pred)
