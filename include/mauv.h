@@ -141,7 +141,9 @@ int mauv_conv2d_bwd_weight_f32(const float* x, const long long* x_strides, const
  * stored tensor then scales with the batch spread |y - mean| instead of |y|, the error the BN's
  * 1/std amplifies when a channel's mean is large.  Every route (the
  * implicit GEMM, 3x3 row images, LDS-DMA tiles, weight-stationary expansion) gives the same bits
- * for the same y_shift. */
+ * for the same y_shift; so does the implicit GEMM's register-staged form that takes the shapes
+ * outside the pipelined kernels (Cin % 64 != 0): the pipelined kernel's bits on the same operands
+ * zero-padded to Cin % 64 == 0, outputs and statistics partials (it shares their epilogue). */
 int mauv_conv2d_fwd_h16(int dtype, const void* x, const long long* x_strides,
                         const float* x_scale, const float* x_shift, int x_relu, const void* w,
                         void* y, int G, int B, int H, int W, int Cin, int Cout, int R, int S,

@@ -1,7 +1,9 @@
 // Shared pieces of the fp32 implicit-GEMM convs (conv_gemm.hip: exact f32 MFMA and the
 // register-staged split path; conv_split.hip: the pipelined split-fp32 kernels): the argument
 // block, the BN-on-load transform and the fused epilogue (bias, residual addend / accumulate,
-// BN statistics partials of the forward, BN-backward partials of the data gradient).
+// BN statistics partials of the forward, BN-backward partials of the data gradient).  The 16-bit
+// convs (conv_gemm16.hip and the kernels it routes to) take the same argument block, built by
+// the same host helpers (make_args, conv_parity_class, conv_stem_row_chunks).
 #pragma once
 #include "h16.h"
 
@@ -158,6 +160,65 @@ bool conv_fwd_batch_chunks(const ConvArgs& a0, long long lim, int esz, F launch)
     if (!launch(c)) return false;
   }
   return true;
+}
+
+// ---- host: the argument block of the C entry points (conv_gemm.hip, conv_gemm16.hip) ----
+// geometry, x strides (xs: {group, batch, h, w, c} in elements, NULL = dense NHWC) and weight
+// stride of one conv; the entry point adds pointers and GEMM dims
+inline ConvArgs make_args(int G, int B, int H, int W, int Cin, int Cout, int R, int S,
+                          int stride, int pad, const long long* xs) {
+  ConvArgs a{};
+  a.G = G; a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.R = R; a.S = S;
+  a.stride = stride; a.pad = pad;
+  a.Ho = (H + 2 * pad - R) / stride + 1;
+  a.Wo = (W + 2 * pad - S) / stride + 1;
+  if (xs) { a.xs_g = xs[0]; a.xs_b = xs[1]; a.xs_h = xs[2]; a.xs_w = xs[3]; a.xs_c = xs[4]; }
+  else {
+    a.xs_c = 1; a.xs_w = Cin; a.xs_h = (long long)W * Cin; a.xs_b = (long long)H * W * Cin;
+    a.xs_g = (long long)B * H * W * Cin;
+  }
+  a.ws_g = (long long)Cout * R * S * Cin;
+  a.splits = 1;
+  return a;
+}
+
+// m-tiles of a launch over M rows (BM = conv_tile_rows(M)) = its per-m-tile BN partials
+inline int stat_blocks(int M) { return ceil_div(M, conv_tile_rows(M)); }
+
+// Output-parity class (ph, pw) of a data gradient (ConvArgs::ph ...): its extent, taps and GEMM
+// dims.  K = 0: no tap reaches the class, which only receives the addend / zeros.
+inline void conv_parity_class(ConvArgs& a, int ph, int pw) {
+  a.ph = ph; a.pw = pw;
+  a.Hc = (a.H - ph + a.stride - 1) / a.stride;
+  a.Wc = (a.W - pw + a.stride - 1) / a.stride;
+  a.r0 = (ph + a.pad) % a.stride;
+  a.s0 = (pw + a.pad) % a.stride;
+  a.nr = a.r0 < a.R ? (a.R - a.r0 + a.stride - 1) / a.stride : 0;
+  a.ns = a.s0 < a.S ? (a.S - a.s0 + a.stride - 1) / a.stride : 0;
+  a.M = a.B * a.Hc * a.Wc;
+  a.K = a.nr * a.ns * a.Cout;
+}
+
+// A stem GEMM over shared im2col rows (a: one 1 x M image of K channels, cpg outputs per group)
+// whose rows exceed the pipelined kernels' 31-bit buffer offsets (configs[4]'s 512 px sonar at
+// B = 256: 16.8 M rows) runs as launches over chunks of whole 128-row tiles, each writing its
+// rows of y and its statistics blocks (st_base).  esz: bytes per element.  Returns the rows
+// launched: a.M when every chunk ran, 0 when the first was declined (nothing launched).
+template <class F>
+long long conv_stem_row_chunks(const ConvArgs& a, int esz, F launch) {
+  const long long lim_rows = (0x7fff0000LL / esz / a.K) / 128 * 128;
+  long long r0 = 0;
+  for (; r0 < a.M; r0 += lim_rows) {
+    ConvArgs c = a;
+    c.M = (int)(a.M - r0 < lim_rows ? a.M - r0 : lim_rows);
+    c.W = c.Wo = c.M;
+    c.xs_h = c.xs_b = (long long)c.M * a.K;
+    c.x = (const float*)((const char*)a.x + r0 * a.K * esz);
+    c.out = (float*)((char*)a.out + r0 * a.cpg * esz);
+    c.st_base = (int)(r0 / 128);
+    if (!launch(c)) return r0;
+  }
+  return a.M;
 }
 
 // Launch the pipelined split-fp32 kernel (conv_split.hip) for an fp32 conv; false when the

@@ -1,11 +1,15 @@
-// Epilogue of the 16-bit implicit-GEMM convs (conv_pipe16.hip) for FWD and
-// DGRAD: BN statistics partials of y from the fp32 accumulators (tile mean, then M2 around it;
-// FWD with st_mean), then the 16-bit output through LDS as 16-byte row chunks (DGRAD: residual
-// addend / previous dx added in fp32, one rounding; parity-class row remap; with bp_p1 the
-// BN-backward partial sums of the BatchNorm whose output gradient dx is).  acc[MI][NI] are
-// this wave's 32 x 32 accumulator tiles (C/D layout of v_mfma_f32_32x32x16: lane l = column
-// l & 31, register r = row (r & 3) + 8 (r >> 2) + 4 (l >> 5)); waves wave = wm * WGN + wn.
-// The caller's main loop ended with a barrier: the LDS (SCRATCH bytes) is free.
+// Shared pieces of every 16-bit implicit-GEMM conv kernel (conv_pipe16, conv_big16, conv_halo16,
+// conv_haloc16, conv_expand16 and the register-staged conv_gemm_h16 of conv_gemm16.hip): the
+// pending BN(+ReLU) of an operand chunk (bn_relu8), the accumulators' start (acc_shift16 /
+// acc_start16) and the FWD / DGRAD epilogue (epilogue16) — one copy of each, so the kernels that
+// keep the implicit GEMM's k order give the same bits for a shape.
+// The epilogue: BN statistics partials of y from the fp32 accumulators (FWD with st_mean), then
+// the 16-bit output through LDS as 16-byte row chunks (DGRAD: residual addend / previous dx
+// added in fp32, one rounding; parity-class row remap; with bp_p1 the BN-backward partial sums
+// of the BatchNorm whose output gradient dx is).  acc[MI][NI] are this wave's 32 x 32
+// accumulator tiles (C/D layout of v_mfma_f32_32x32x16: lane l = column l & 31, register r = row
+// (r & 3) + 8 (r >> 2) + 4 (l >> 5)); waves wave = wm * WGN + wn.  The caller's main loop ended
+// with a barrier: the LDS (SCRATCH bytes) is free.
 #pragma once
 #include "conv_common.h"
 

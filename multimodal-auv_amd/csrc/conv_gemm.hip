@@ -580,33 +580,15 @@ static void launch_tiles(const ConvArgs& a, hipStream_t st) {
 
 using namespace mauv;
 
-// m-tiles of a launch (BM = conv_tile_rows(M)), = per-m-tile BN statistic partials
-static int stat_blocks(int M, int N, int G) { return ceil_div(M, conv_tile_rows(M)); }
-static int dgrad_stat_blocks(int G, int B, int H, int W, int N, int stride) {
+// per-m-tile BN-backward partials of a data gradient: the m-tiles of its parity classes
+static int dgrad_stat_blocks(int B, int H, int W, int stride) {
   int n = 0;
   for (int ph = 0; ph < stride; ++ph)
     for (int pw = 0; pw < stride; ++pw) {
       const int M = B * ((H - ph + stride - 1) / stride) * ((W - pw + stride - 1) / stride);
-      if (M > 0) n += stat_blocks(M, N, G);
+      if (M > 0) n += stat_blocks(M);
     }
   return n;
-}
-
-static ConvArgs make_args(int G, int B, int H, int W, int Cin, int Cout, int R, int S,
-                          int stride, int pad, const long long* xs) {
-  ConvArgs a{};
-  a.G = G; a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.R = R; a.S = S;
-  a.stride = stride; a.pad = pad;
-  a.Ho = (H + 2 * pad - R) / stride + 1;
-  a.Wo = (W + 2 * pad - S) / stride + 1;
-  if (xs) { a.xs_g = xs[0]; a.xs_b = xs[1]; a.xs_h = xs[2]; a.xs_w = xs[3]; a.xs_c = xs[4]; }
-  else {
-    a.xs_c = 1; a.xs_w = Cin; a.xs_h = (long long)W * Cin; a.xs_b = (long long)H * W * Cin;
-    a.xs_g = (long long)B * H * W * Cin;
-  }
-  a.ws_g = (long long)Cout * R * S * Cin;
-  a.splits = 1;
-  return a;
 }
 
 // Forward: y[g] = conv(x[g], W_g) (+ bias[g]) — NHWC, fp32.
@@ -626,7 +608,7 @@ MAUV_API int mauv_conv2d_fwd_f32(const float* x, const long long* x_strides,
   a.M = B * a.Ho * a.Wo; a.N = Cout; a.K = R * S * Cin;
   a.out_sg = (long long)a.M * a.N;
   a.st_mean = st_mean; a.st_m2 = st_m2; a.st_cnt = st_cnt;
-  a.st_nblk = stat_blocks(a.M, a.N, G); a.st_base = 0;
+  a.st_nblk = stat_blocks(a.M);
   const bool va = (Cin % 32 == 0) && a.xs_c == 1 && (a.xs_w % 4 == 0) && (a.xs_h % 4 == 0) &&
                   (a.xs_b % 4 == 0) && (a.xs_g % 4 == 0);
   const bool vb = (a.K % 4 == 0);
@@ -652,26 +634,15 @@ MAUV_API int mauv_stem_fwd_f32(const float* cols, const float* w, float* y, int 
   a.out_sg = (long long)M * Cout;
   a.cpg = Cout;
   a.st_mean = st_mean; a.st_m2 = st_m2; a.st_cnt = st_cnt;
-  a.st_nblk = stat_blocks(M, Cout, G); a.st_base = 0;
+  a.st_nblk = stat_blocks(M);
   const int fm = f32_math();
   if (fm == 6 || fm == 5) {
-    // the split kernel reads cols by a buffer descriptor (31-bit byte offsets): more rows
-    // (configs[4]'s 512 px sonar at B = 256) go in chunks of whole 128-row tiles, each writing
-    // its rows of y and its statistics blocks (st_base)
-    const long long lim_rows = (0x7fff0000LL / 4 / Kp) / 128 * 128;
-    bool ok = true;
-    for (long long r0 = 0; r0 < M && ok; r0 += lim_rows) {
-      ConvArgs c = a;
-      c.M = (int)(M - r0 < lim_rows ? M - r0 : lim_rows);
-      c.W = c.Wo = c.M;                        // cols as one 1 x M image of Kp channels
-      c.xs_h = c.xs_b = (long long)c.M * Kp;
-      c.x = cols + r0 * Kp;
-      c.out = y + r0 * Cout;
-      c.st_base = (int)(r0 / 128);
-      ok = conv_split_launch(FWD, c, fm == 5, stream);
-      if (!ok && r0 > 0) { set_error("stem_fwd_f32: chunk outside the split kernel"); return kErrArg; }
-    }
-    if (ok) return check_launch("stem_fwd_f32");
+    // the split kernel reads cols by a buffer descriptor: in row chunks (conv_stem_row_chunks)
+    const long long rows = conv_stem_row_chunks(a, 4, [&](const ConvArgs& c) {
+      return conv_split_launch(FWD, c, fm == 5, stream);
+    });
+    if (rows == M) return check_launch("stem_fwd_f32");
+    if (rows > 0) { set_error("stem_fwd_f32: chunk outside the split kernel"); return kErrArg; }
   }
   if (Kp % 32 == 0) launch_tiles<FWD, true, true>(a, stream);
   else launch_tiles<FWD, false, true>(a, stream);
@@ -696,22 +667,13 @@ MAUV_API int mauv_conv2d_bwd_data_f32(const float* dy, const float* w, float* dx
   a.bp_y = bn_y; a.bp_out = bn_out; a.bp_mask = bn_mask; a.bp_sc = bn_scale; a.bp_sh = bn_shift;
   a.bp_mean = bn_mean; a.bp_invstd = bn_invstd; a.bp_relu = bn_relu;
   a.bp_p1 = bn_p1; a.bp_p2 = bn_p2;
-  a.bp_nblk = dgrad_stat_blocks(G, B, H, W, Cin, stride);
-  a.bp_base = 0;
+  a.bp_nblk = dgrad_stat_blocks(B, H, W, stride);
   if (bn_p1 && bn_relu && !bn_out && !bn_mask && !bn_shift) { set_error("conv2d_bwd_data: mask source"); return kErrArg; }
   const bool va = (Cout % 32 == 0), vb = (Cin % 4 == 0);
   // one launch per output-parity class (stride^2 of them; 1 for stride 1)
   for (int ph = 0; ph < stride; ++ph)
     for (int pw = 0; pw < stride; ++pw) {
-      a.ph = ph; a.pw = pw;
-      a.Hc = (H - ph + stride - 1) / stride;
-      a.Wc = (W - pw + stride - 1) / stride;
-      a.r0 = (ph + pad) % stride;
-      a.s0 = (pw + pad) % stride;
-      a.nr = a.r0 < R ? (R - a.r0 + stride - 1) / stride : 0;
-      a.ns = a.s0 < S ? (S - a.s0 + stride - 1) / stride : 0;
-      a.M = B * a.Hc * a.Wc;
-      a.K = a.nr * a.ns * Cout;  // 0 -> the class only receives the addend / zeros
+      conv_parity_class(a, ph, pw);
       if (a.M <= 0) continue;
       // a tapless class accumulating into dx adds nothing (stride-2 1x1 downsample: 3 of 4)
       if (a.K == 0 && accumulate && !addend && !bn_p1) continue;
@@ -720,7 +682,7 @@ MAUV_API int mauv_conv2d_bwd_data_f32(const float* dy, const float* w, float* dx
       else if (va && vb) launch_tiles<DGRAD, true, true>(a, stream);
       else if (vb) launch_tiles<DGRAD, false, true>(a, stream);
       else launch_tiles<DGRAD, false, false>(a, stream);
-      a.bp_base += stat_blocks(a.M, a.N, G);
+      a.bp_base += stat_blocks(a.M);
     }
   return check_launch("conv2d_bwd_data");
 }
@@ -730,11 +692,11 @@ MAUV_API int mauv_conv2d_bwd_data_f32(const float* dy, const float* w, float* dx
 MAUV_API int mauv_conv2d_fwd_stat_blocks(int G, int B, int H, int W, int Cin, int Cout, int R,
                                          int S, int stride, int pad) {
   const int Ho = (H + 2 * pad - R) / stride + 1, Wo = (W + 2 * pad - S) / stride + 1;
-  return stat_blocks(B * Ho * Wo, Cout, G);
+  return stat_blocks(B * Ho * Wo);
 }
 MAUV_API int mauv_conv2d_bwd_data_stat_blocks(int G, int B, int H, int W, int Cin, int Cout,
                                               int R, int S, int stride, int pad) {
-  return dgrad_stat_blocks(G, B, H, W, Cin, stride);
+  return dgrad_stat_blocks(B, H, W, stride);
 }
 
 // Split count used by mauv_conv2d_bwd_weight for a given problem (host helper so the caller

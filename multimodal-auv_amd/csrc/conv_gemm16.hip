@@ -1,4 +1,12 @@
-// Implicit-GEMM convolution on CDNA4 16-bit MFMA (bf16 / f16 operands, fp32 accumulation).
+// Implicit-GEMM convolution on CDNA4 16-bit MFMA (bf16 / f16 operands, fp32 accumulation): the
+// C entry points of the 16-bit convs and the register-staged kernel conv_gemm_h16, which runs
+// every shape outside the pipelined kernels (conv_pipe16.hip and the families it routes to):
+// forwards with Cin % 64 != 0, data gradients with Cout % 64 != 0, weight gradients over rows or
+// columns of more than 4096 output pixels, tensors beyond 31-bit byte offsets (it addresses by
+// 64-bit pointers).  It takes the pipelined kernels' argument block (ConvArgs) and their shared
+// pieces — conv_block_tile, acc_shift16 / acc_start16, bn_relu8, epilogue16 (conv_epi16.h) and
+// the weight gradient's conv_epilogue (conv_common.h) — so its outputs and statistics partials
+// are the pipelined kernel's bits on the same operands zero-padded to its channel multiples.
 //
 // The reduced-precision counterpart of conv_gemm.hip for BASELINE configs[2] (bf16 training)
 // and the reference predictor's autocast inference (inference/predictors.py:55): the same three
@@ -23,95 +31,44 @@
 //                            an operand fragment is two ds_read_b64_tr_b16 hardware-transposed
 //                            reads; the 64-B pad makes a 32-lane half's 4 rows x 64 B cover
 //                            the 64 banks once (conflict-free).
-// 256 threads = 4 waves (2x2), wave tile (BM/2)x(BN/2) = 2x2 MFMA tiles of 32x32.
+// 256 threads = 4 waves (2x2), wave tile (BM/2)x(BN/2) = 1 or 2 MFMA tiles of 32x32 each way.
 #include <stdlib.h>
 
 #include "conv_common.h"
+#include "conv_epi16.h"
 
 namespace mauv {
-
-enum { H_FWD = 0, H_DGRAD = 1, H_WGRAD = 2 };
-
-struct ConvArgs16 {
-  int B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad;
-  long long xs_g, xs_b, xs_h, xs_w;  // x element strides (channel stride 1)
-  const u16* x;
-  const u16* w;  // [G][Cout][R][S][Cin]
-  long long ws_g;
-  const u16* dy;  // [G][B*Ho*Wo][Cout]
-  void* out;      // FWD/DGRAD: 16-bit [G][M][N]; WGRAD: fp32 slabs [splits][G][M][N]
-  long long out_sg;
-  const u16* addend;
-  int accumulate;
-  int G, splits, kchunk;
-  int M, N, K;
-  int ph, pw, Hc, Wc, r0, s0, nr, ns;  // DGRAD output-parity class
-  const float* xsc;                    // lazy BN(+ReLU) of x on load (FWD A, WGRAD B)
-  const float* xsh;
-  int xrelu;
-  float *st_mean, *st_m2, *st_cnt;  // FWD epilogue BN statistics partials
-  int st_nblk;
-  const float* ysh;                 // FWD: centred storage (conv_common.h ConvArgs::ysh)
-};
 
 constexpr int HBK = 32;
 constexpr int RLD = HBK + 8;
 __host__ __device__ constexpr int cld(int rows) { return rows + 32; }
 
-template <int DT>
-__device__ __forceinline__ u32x4 bn_chunk(u32x4 v, const float* sc, const float* sh, int relu) {
-  floatx8 f = unpack8<DT>(v);
-  const floatx4 s0 = *(const floatx4*)sc, s1 = *(const floatx4*)(sc + 4);
-  const floatx4 h0 = *(const floatx4*)sh, h1 = *(const floatx4*)(sh + 4);
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    f[e] = f[e] * s0[e] + h0[e];
-    f[4 + e] = f[4 + e] * s1[e] + h1[e];
-  }
-  if (relu) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) f[e] = f[e] > 0.f ? f[e] : 0.f;
-  }
-  return pack8<DT>(f);
-}
-
-// operand fragment of 32 rows (R0..R0+31) for k-step s from a row image
-__device__ __forceinline__ u32x4 row_frag(const u16* img, int R0, int s, int li, int lh) {
-  return *(const u32x4*)(img + (R0 + li) * RLD + 16 * s + 8 * lh);
-}
-// ... and from a col image with leading dimension LD: col_frag (h16.h)
-
 template <int MODE, int DT, int BM, int BN, bool TAPU>
-__global__ __launch_bounds__(256) void conv_gemm_h16(const ConvArgs16 a) {
-  constexpr bool A_COL = (MODE == H_WGRAD);
-  constexpr bool B_COL = (MODE != H_FWD);
+__global__ __launch_bounds__(256) void conv_gemm_h16(const ConvArgs a) {
+  constexpr bool A_COL = (MODE == WGRAD);
+  constexpr bool B_COL = (MODE != FWD);
   constexpr int A_SZ = A_COL ? HBK * cld(BM) : BM * RLD;
   constexpr int B_SZ = B_COL ? HBK * cld(BN) : BN * RLD;
   constexpr int STG = A_SZ + B_SZ;
   constexpr int WM = BM / 2, WN = BN / 2, MI = WM / 32, NI = WN / 32;
   constexpr int NA = BM / 64, NB = BN / 64;  // 16-B chunks per thread per stage
+  static_assert(2 * STG >= 2 * WM * (BN + 4) && 2 * STG >= 16 * BN, "epilogue scratch");
   __shared__ __attribute__((aligned(16))) u16 smem[2 * STG];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
   const int li = lane & 31, lh = lane >> 5;
-  int m0, n0;
-  {  // XCD-aware tile order (as conv_gemm.hip): n-fastest logical tiles kept on one XCD
-    const int nN = (a.N + BN - 1) / BN;
-    const int b = blockIdx.x, nwg = gridDim.x, xcd = b & 7, q = nwg >> 3, r = nwg & 7;
-    const int L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-    m0 = (L / nN) * BM;
-    n0 = (L - (L / nN) * nN) * BN;
-  }
+  int m0, n0, by;
+  conv_block_tile<BM, BN>(a, m0, n0, by);  // xcd_grid = 0: XCD-aware order over blockIdx.x
   int g, sp = 0;
-  if constexpr (MODE == H_WGRAD) { g = blockIdx.y / a.splits; sp = blockIdx.y % a.splits; }
-  else g = blockIdx.y;
+  if constexpr (MODE == WGRAD) { g = by / a.splits; sp = by % a.splits; }
+  else g = by;
   int kbeg = 0, kend = a.K;
-  if constexpr (MODE == H_WGRAD) { kbeg = sp * a.kchunk; kend = min(a.K, kbeg + a.kchunk); }
+  if constexpr (MODE == WGRAD) { kbeg = sp * a.kchunk; kend = min(a.K, kbeg + a.kchunk); }
 
-  const u16* xg = a.x + (long long)g * a.xs_g;
-  const u16* wg = a.w + (long long)g * a.ws_g;
-  const u16* dyg = a.dy + (long long)g * ((long long)a.B * a.Ho * a.Wo * a.Cout);
+  const u16* xg = (const u16*)a.x + (long long)g * a.xs_g;
+  const u16* wg = (const u16*)a.w + (long long)g * a.ws_g;
+  const u16* dyg = (const u16*)a.dy + (long long)g * ((long long)a.B * a.Ho * a.Wo * a.Cout);
 
   // ---------------- per-thread loader state ----------------
   long long a_base[NA];
@@ -124,14 +81,14 @@ __global__ __launch_bounds__(256) void conv_gemm_h16(const ConvArgs16 a) {
   // A
 #pragma unroll
   for (int j = 0; j < NA; ++j) {
-    if constexpr (MODE == H_FWD || MODE == H_DGRAD) {
+    if constexpr (MODE == FWD || MODE == DGRAD) {
       const int m = m0 + (tid >> 2) + 64 * j;
       a_ok[j] = m < a.M;
       const int mm = a_ok[j] ? m : 0;
-      const int HW = (MODE == H_FWD) ? a.Ho * a.Wo : a.Hc * a.Wc;
-      const int WW = (MODE == H_FWD) ? a.Wo : a.Wc;
+      const int HW = (MODE == FWD) ? a.Ho * a.Wo : a.Hc * a.Wc;
+      const int WW = (MODE == FWD) ? a.Wo : a.Wc;
       const int b = mm / HW, rem = mm - b * HW, oh = rem / WW, ow = rem - oh * WW;
-      if constexpr (MODE == H_FWD) {
+      if constexpr (MODE == FWD) {
         a_base[j] = (long long)b * a.xs_b;
         a_p0[j] = oh * a.stride - a.pad;
         a_p1[j] = ow * a.stride - a.pad;
@@ -153,11 +110,11 @@ __global__ __launch_bounds__(256) void conv_gemm_h16(const ConvArgs16 a) {
 #pragma unroll
   for (int j = 0; j < NB; ++j) {
     const int idx = tid + 256 * j;
-    if constexpr (MODE == H_FWD) {
+    if constexpr (MODE == FWD) {
       const int n = n0 + (tid >> 2) + 64 * j;
       b_ok[j] = n < a.N;
       b_r[j] = b_ok[j] ? n : 0;
-    } else if constexpr (MODE == H_DGRAD) {
+    } else if constexpr (MODE == DGRAD) {
       b_r[j] = idx / (BN / 8);              // k row within the stage
       b_c[j] = n0 + 8 * (idx % (BN / 8));   // cin
       b_ok[j] = b_c[j] < a.N;
@@ -176,10 +133,8 @@ __global__ __launch_bounds__(256) void conv_gemm_h16(const ConvArgs16 a) {
       px_h[j] = rem / a.Wo;
       px_w[j] = rem - px_h[j] * a.Wo;
       if (a.xsc && b_ok[j]) {
-        const float* s = a.xsc + g * a.Cin + b_c[j];
-        const float* h = a.xsh + g * a.Cin + b_c[j];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { bsc[j][e] = s[e]; bsh[j][e] = h[e]; }
+        bsc[j] = ldf8(a.xsc + g * a.Cin + b_c[j]);
+        bsh[j] = ldf8(a.xsh + g * a.Cin + b_c[j]);
       }
     }
   }
@@ -189,12 +144,13 @@ __global__ __launch_bounds__(256) void conv_gemm_h16(const ConvArgs16 a) {
 
   u32x4 ra[NA], rb[NB];
   const u32x4 zero = {0u, 0u, 0u, 0u};
+  const unsigned rfloor = a.xrelu ? 0u : 0x80008000u;  // bn_relu8's ReLU floor
 
   auto load = [&](int k0) {
 #pragma unroll
     for (int j = 0; j < NA; ++j) {
       u32x4 v = zero;
-      if constexpr (MODE == H_FWD) {
+      if constexpr (MODE == FWD) {
         int r, s, c;
         bool kok = true;
         if constexpr (TAPU) {
@@ -210,9 +166,10 @@ __global__ __launch_bounds__(256) void conv_gemm_h16(const ConvArgs16 a) {
         const int ih = a_p0[j] + r, iw = a_p1[j] + s;
         if (a_ok[j] && kok && ih >= 0 && ih < a.H && iw >= 0 && iw < a.W) {
           v = *(const u32x4*)(xg + a_base[j] + (long long)ih * a.xs_h + (long long)iw * a.xs_w + c);
-          if (a.xsc) v = bn_chunk<DT>(v, a.xsc + g * a.Cin + c, a.xsh + g * a.Cin + c, a.xrelu);
+          if (a.xsc)
+            v = bn_relu8<DT>(v, ldf8(a.xsc + g * a.Cin + c), ldf8(a.xsh + g * a.Cin + c), rfloor, true);
         }
-      } else if constexpr (MODE == H_DGRAD) {
+      } else if constexpr (MODE == DGRAD) {
         const int ohn = a_p0[j] - a.r0 - a.stride * t_r, own = a_p1[j] - a.s0 - a.stride * t_s;
         if (a_ok[j] && ohn >= 0 && own >= 0) {
           const int oh = a.stride == 1 ? ohn : ohn / a.stride;
@@ -229,10 +186,10 @@ __global__ __launch_bounds__(256) void conv_gemm_h16(const ConvArgs16 a) {
 #pragma unroll
     for (int j = 0; j < NB; ++j) {
       u32x4 v = zero;
-      if constexpr (MODE == H_FWD) {
+      if constexpr (MODE == FWD) {
         const int k = k0 + 8 * kc;
         if (b_ok[j] && k < kend) v = *(const u32x4*)(wg + (long long)b_r[j] * a.K + k);
-      } else if constexpr (MODE == H_DGRAD) {
+      } else if constexpr (MODE == DGRAD) {
         const int n = t_c + b_r[j];
         const int r = a.r0 + a.stride * t_r, s = a.s0 + a.stride * t_s;
         if (b_ok[j]) v = *(const u32x4*)(wg + (((long long)n * a.R + r) * a.S + s) * a.Cin + b_c[j]);
@@ -244,15 +201,7 @@ __global__ __launch_bounds__(256) void conv_gemm_h16(const ConvArgs16 a) {
           if (ih >= 0 && ih < a.H && iw >= 0 && iw < a.W) {
             v = *(const u32x4*)(xg + (long long)px_b[j] * a.xs_b + (long long)ih * a.xs_h +
                                 (long long)iw * a.xs_w + b_c[j]);
-            if (a.xsc) {
-              floatx8 f = unpack8<DT>(v);
-#pragma unroll
-              for (int e = 0; e < 8; ++e) {
-                f[e] = f[e] * bsc[j][e] + bsh[j][e];
-                if (a.xrelu) f[e] = f[e] > 0.f ? f[e] : 0.f;
-              }
-              v = pack8<DT>(f);
-            }
+            if (a.xsc) v = bn_relu8<DT>(v, bsc[j], bsh[j], rfloor, true);
           }
         }
         // advance this chunk's pixel by one stage
@@ -263,10 +212,10 @@ __global__ __launch_bounds__(256) void conv_gemm_h16(const ConvArgs16 a) {
       rb[j] = v;
     }
     // advance the tile-uniform tap counters by one stage
-    if constexpr ((MODE == H_FWD && TAPU)) {
+    if constexpr ((MODE == FWD && TAPU)) {
       t_c += HBK;
       if (t_c >= a.Cin) { t_c = 0; if (++t_s == a.S) { t_s = 0; ++t_r; } }
-    } else if constexpr (MODE == H_DGRAD) {
+    } else if constexpr (MODE == DGRAD) {
       t_c += HBK;
       if (t_c >= a.Cout) { t_c = 0; if (++t_s == a.ns) { t_s = 0; ++t_r; } }
     }
@@ -296,18 +245,13 @@ __global__ __launch_bounds__(256) void conv_gemm_h16(const ConvArgs16 a) {
   };
 
   floatx16 acc[MI][NI];
-#pragma unroll
-  for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
+  float cs[NI];  // the accumulators' start (conv_epi16.h): loaded here, filled behind the loads
+  acc_shift16(cs, a, n0 + wn * WN, MODE == FWD);
 
   const int ntiles = (kend - kbeg + HBK - 1) / HBK;
-  if (ntiles > 0) {
-    load(kbeg);
-    store(0);
-  }
+  if (ntiles > 0) load(kbeg);
+  acc_start16(acc, cs);
+  if (ntiles > 0) store(0);
   __syncthreads();
   int cur = 0;
   for (int t = 0; t < ntiles; ++t) {
@@ -321,11 +265,11 @@ __global__ __launch_bounds__(256) void conv_gemm_h16(const ConvArgs16 a) {
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi)
         af[mi] = A_COL ? col_frag(A, cld(BM), wm * WM + mi * 32, s, lane)
-                       : row_frag(A, wm * WM + mi * 32, s, li, lh);
+                       : row_frag_ld<RLD>(A, wm * WM + mi * 32, s, li, lh);
 #pragma unroll
       for (int ni = 0; ni < NI; ++ni)
         bfr[ni] = B_COL ? col_frag(Bm, cld(BN), wn * WN + ni * 32, s, lane)
-                        : row_frag(Bm, wn * WN + ni * 32, s, li, lh);
+                        : row_frag_ld<RLD>(Bm, wn * WN + ni * 32, s, li, lh);
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
@@ -336,148 +280,21 @@ __global__ __launch_bounds__(256) void conv_gemm_h16(const ConvArgs16 a) {
     cur ^= 1;
   }
 
-  // ---------------- epilogue ----------------
-  if ((MODE == H_FWD) && a.ysh) {  // centred storage (conv_epi16.h acc_start16's semantics)
-#pragma unroll
-    for (int ni = 0; ni < NI; ++ni) {
-      const int col = n0 + wn * WN + ni * 32 + li;
-      const float c = col < a.N ? a.ysh[col] : 0.f;
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[mi][ni][r] -= c;
-    }
-  }
-  // FWD statistics (from the fp32 accumulators, before any rounding)
-  if ((MODE == H_FWD) && a.st_mean) {
-    const int nvalid = min(BM, a.M - m0);
-    float s1[NI], s2[NI], mean[NI];
-#pragma unroll
-    for (int ni = 0; ni < NI; ++ni) { s1[ni] = 0.f; s2[ni] = 0.f; }
-#pragma unroll
-    for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = m0 + wm * WM + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-          if (row < a.M) s1[ni] += acc[mi][ni][r];
-        }
-    float* red = (float*)smem;  // LDS is free: the main loop ended with a barrier
-    const int tcol = wn * WN + li;
-#pragma unroll
-    for (int ni = 0; ni < NI; ++ni) s1[ni] += __shfl_xor(s1[ni], 32, 64);
-    if (lh == 0) {
-#pragma unroll
-      for (int ni = 0; ni < NI; ++ni) red[wm * BN + tcol + ni * 32] = s1[ni];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int ni = 0; ni < NI; ++ni)
-      mean[ni] = (red[tcol + ni * 32] + red[BN + tcol + ni * 32]) / (float)nvalid;
-#pragma unroll
-    for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = m0 + wm * WM + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-          if (row < a.M) {
-            const float d = acc[mi][ni][r] - mean[ni];
-            s2[ni] += d * d;
-          }
-        }
-#pragma unroll
-    for (int ni = 0; ni < NI; ++ni) s2[ni] += __shfl_xor(s2[ni], 32, 64);
-    if (lh == 0) {
-#pragma unroll
-      for (int ni = 0; ni < NI; ++ni) red[2 * BN + wm * BN + tcol + ni * 32] = s2[ni];
-    }
-    __syncthreads();
-    if (tid < BN && n0 + tid < a.N) {
-      const float t1 = red[tid] + red[BN + tid], t2 = red[2 * BN + tid] + red[3 * BN + tid];
-      const int mt = m0 / BM;
-      const long long so = ((long long)g * a.st_nblk + mt) * a.N + n0 + tid;
-      a.st_mean[so] = t1 / (float)nvalid;
-      a.st_m2[so] = t2;
-      if (n0 + tid == 0) a.st_cnt[(long long)g * a.st_nblk + mt] = (float)nvalid;
-    }
-    __syncthreads();  // red is overwritten by the staged store below
-  }
-
-  if constexpr (MODE == H_WGRAD) {  // fp32 split-K slabs: 32 lanes x 4 B contiguous per store
-    float* outg = (float*)a.out + ((long long)sp * a.G + g) * ((long long)a.M * a.N);
-#pragma unroll
-    for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < NI; ++ni) {
-        const int col = n0 + wn * WN + ni * 32 + li;
-        if (col >= a.N) continue;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = m0 + wm * WM + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-          if (row < a.M) outg[(long long)row * a.N + col] = acc[mi][ni][r];
-        }
-      }
-  } else {
-    // 16-bit output through LDS: each wave row (wm = 0, 1) in turn parks its fp32 accumulators
-    // as a [WM][BN+4] tile, then all 256 threads write it out as 16-byte rows of 8 channels
-    // (adding the residual addend / previous dx in fp32, one rounding).
-    constexpr int SLD = BN + 4;
-    static_assert(WM * SLD * 4 <= 2 * STG * 2, "staging tile exceeds LDS");
-    float* stile = (float*)smem;
-    constexpr int CPR = BN / 8, NCH = WM * CPR;
-    u16* outp = (u16*)a.out;
-#pragma unroll
-    for (int pass = 0; pass < 2; ++pass) {
-      if (wm == pass) {
-#pragma unroll
-        for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-          for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-              stile[(mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * SLD + wn * WN + ni * 32 + li] =
-                  acc[mi][ni][r];
-      }
-      __syncthreads();
-      for (int c = tid; c < NCH; c += 256) {
-        const int rl = c / CPR, cc = c - rl * CPR;
-        const int row = m0 + pass * WM + rl, col = n0 + 8 * cc;
-        if (row >= a.M || col >= a.N) continue;
-        floatx4 v0 = *(const floatx4*)(stile + rl * SLD + 8 * cc);
-        floatx4 v1 = *(const floatx4*)(stile + rl * SLD + 8 * cc + 4);
-        floatx8 f;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { f[e] = v0[e]; f[4 + e] = v1[e]; }
-        long long orow = row;
-        if constexpr (MODE == H_DGRAD) {
-          if (a.stride != 1) {
-            const int HW = a.Hc * a.Wc, b = row / HW, rem = row - b * HW;
-            const int i = rem / a.Wc, jj = rem - i * a.Wc;
-            orow = ((long long)b * a.H + a.stride * i + a.ph) * a.W + a.stride * jj + a.pw;
-          }
-        }
-        const long long o = (long long)g * a.out_sg + orow * a.N + col;
-        if constexpr (MODE == H_DGRAD) {
-          if (a.addend) f += unpack8<DT>(*(const u32x4*)(a.addend + o));
-          if (a.accumulate) f += unpack8<DT>(*(const u32x4*)(outp + o));
-        }
-        *(u32x4*)(outp + o) = pack8<DT>(f);
-      }
-      __syncthreads();
-    }
-  }
+  // ---------------- epilogue (shared with the pipelined kernels) ----------------
+  if constexpr (MODE == WGRAD)
+    conv_epilogue<WGRAD, BM, BN, MI, NI, 2, 2>(a, acc, (float*)smem, tid, m0, n0, g, sp);
+  else
+    epilogue16<MODE, DT, BM, BN, MI, NI, 2, 2, sizeof(smem)>(a, acc, smem, m0, n0, g);
 }
 
 template <int MODE, int DT, int BM, int BN, bool TAPU>
-static void launch16(const ConvArgs16& a, hipStream_t st) {
-  dim3 grid(ceil_div(a.M, BM) * ceil_div(a.N, BN), MODE == H_WGRAD ? a.G * a.splits : a.G);
+static void launch16(const ConvArgs& a, hipStream_t st) {
+  dim3 grid(ceil_div(a.M, BM) * ceil_div(a.N, BN), MODE == WGRAD ? a.G * a.splits : a.G);
   hipLaunchKernelGGL((conv_gemm_h16<MODE, DT, BM, BN, TAPU>), grid, dim3(256), 0, st, a);
 }
 
 template <int MODE, int DT, bool TAPU>
-static void tiles16(const ConvArgs16& a, hipStream_t st) {
+static void tiles16(const ConvArgs& a, hipStream_t st) {
   const int bm = conv_tile_rows(a.M), bn = conv_tile_rows(a.N);
   if (bm == 64 && bn == 64) launch16<MODE, DT, 64, 64, TAPU>(a, st);
   else if (bm == 64) launch16<MODE, DT, 64, 128, TAPU>(a, st);
@@ -486,46 +303,12 @@ static void tiles16(const ConvArgs16& a, hipStream_t st) {
 }
 
 template <int MODE, bool TAPU>
-static void dispatch16(int dt, const ConvArgs16& a, hipStream_t st) {
+static void dispatch16(int dt, const ConvArgs& a, hipStream_t st) {
   if (dt == DT_BF16) tiles16<MODE, DT_BF16, TAPU>(a, st);
   else tiles16<MODE, DT_F16, TAPU>(a, st);
 }
 
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-static ConvArgs16 make_args16(int G, int B, int H, int W, int Cin, int Cout, int R, int S,
-                              int stride, int pad, const long long* xs) {
-  ConvArgs16 a{};
-  a.G = G; a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.R = R; a.S = S;
-  a.stride = stride; a.pad = pad;
-  a.Ho = (H + 2 * pad - R) / stride + 1;
-  a.Wo = (W + 2 * pad - S) / stride + 1;
-  if (xs) { a.xs_g = xs[0]; a.xs_b = xs[1]; a.xs_h = xs[2]; a.xs_w = xs[3]; }
-  else {
-    a.xs_w = Cin; a.xs_h = (long long)W * Cin; a.xs_b = (long long)H * W * Cin;
-    a.xs_g = (long long)B * H * W * Cin;
-  }
-  a.ws_g = (long long)Cout * R * S * Cin;
-  a.splits = 1;
-  return a;
-}
-
-// the pipelined kernels (conv_pipe16.hip) take the fp32 argument block with 16-bit pointers
-static ConvArgs pipe_args(const ConvArgs16& h) {
-  ConvArgs a{};
-  a.B = h.B; a.H = h.H; a.W = h.W; a.Cin = h.Cin; a.Ho = h.Ho; a.Wo = h.Wo; a.Cout = h.Cout;
-  a.R = h.R; a.S = h.S; a.stride = h.stride; a.pad = h.pad;
-  a.xs_g = h.xs_g; a.xs_b = h.xs_b; a.xs_h = h.xs_h; a.xs_w = h.xs_w; a.xs_c = 1;
-  a.x = (const float*)h.x; a.w = (const float*)h.w; a.ws_g = h.ws_g; a.dy = (const float*)h.dy;
-  a.out = (float*)h.out; a.out_sg = h.out_sg; a.addend = (const float*)h.addend;
-  a.accumulate = h.accumulate; a.G = h.G; a.splits = h.splits; a.kchunk = h.kchunk;
-  a.M = h.M; a.N = h.N; a.K = h.K;
-  a.ph = h.ph; a.pw = h.pw; a.Hc = h.Hc; a.Wc = h.Wc; a.r0 = h.r0; a.s0 = h.s0; a.nr = h.nr;
-  a.ns = h.ns; a.xsc = h.xsc; a.xsh = h.xsh; a.xrelu = h.xrelu;
-  a.st_mean = h.st_mean; a.st_m2 = h.st_m2; a.st_cnt = h.st_cnt; a.st_nblk = h.st_nblk;
-  a.ysh = h.ysh;
-  return a;
-}
 
 static int check_shape16(const char* what, int dt, int G, int B, int Cin, int Cout,
                          const long long* xs) {
@@ -551,17 +334,17 @@ MAUV_API int mauv_conv2d_fwd_h16(int dtype, const void* x, const long long* x_st
                                  hipStream_t stream) {
   if (int e = check_shape16("conv2d_fwd_h16", dtype, G, B, Cin, Cout, x_strides)) return e;
   if (!aligned16(x) || !aligned16(w)) { set_error("conv2d_fwd_h16: x, w must be 16-B aligned"); return kErrArg; }
-  ConvArgs16 a = make_args16(G, B, H, W, Cin, Cout, R, S, stride, pad, x_strides);
-  a.x = (const u16*)x; a.w = (const u16*)w; a.out = y;
+  ConvArgs a = make_args(G, B, H, W, Cin, Cout, R, S, stride, pad, x_strides);
+  a.x = (const float*)x; a.w = (const float*)w; a.out = (float*)y;
   a.xsc = x_scale; a.xsh = x_shift; a.xrelu = x_relu;
   a.M = B * a.Ho * a.Wo; a.N = Cout; a.K = R * S * Cin;
   a.out_sg = (long long)a.M * a.N;
   a.st_mean = st_mean; a.st_m2 = st_m2; a.st_cnt = st_cnt;
-  a.st_nblk = ceil_div(a.M, conv_tile_rows(a.M));
+  a.st_nblk = stat_blocks(a.M);
   a.ysh = y_shift;
-  if (conv_pipe16_launch(FWD, dtype, pipe_args(a), stream)) {}
-  else if (Cin % HBK == 0) dispatch16<H_FWD, true>(dtype, a, stream);
-  else dispatch16<H_FWD, false>(dtype, a, stream);
+  if (conv_pipe16_launch(FWD, dtype, a, stream)) {}
+  else if (Cin % HBK == 0) dispatch16<FWD, true>(dtype, a, stream);
+  else dispatch16<FWD, false>(dtype, a, stream);
   return check_launch("conv2d_fwd_h16");
 }
 
@@ -588,15 +371,14 @@ MAUV_API int mauv_conv2d_fwd_fold_h16(int dtype, const void* y, const float* sca
     set_error("conv2d_fwd_fold_h16: y, res, out, w must be 16-B aligned");
     return kErrArg;
   }
-  ConvArgs16 h = make_args16(G, B, H, W, Cin, Cout, 1, 1, 1, 0, nullptr);
-  h.x = (const u16*)y; h.w = (const u16*)w; h.out = y1;
-  h.xsc = scale; h.xsh = shift; h.xrelu = 1;
-  h.M = B * H * W; h.N = Cout; h.K = Cin;
-  h.out_sg = (long long)h.M * h.N;
-  h.st_mean = st_mean; h.st_m2 = st_m2; h.st_cnt = st_cnt;
-  h.st_nblk = ceil_div(h.M, conv_tile_rows(h.M));
-  h.ysh = y1_shift;
-  ConvArgs a = pipe_args(h);
+  ConvArgs a = make_args(G, B, H, W, Cin, Cout, 1, 1, 1, 0, nullptr);
+  a.x = (const float*)y; a.w = (const float*)w; a.out = (float*)y1;
+  a.xsc = scale; a.xsh = shift; a.xrelu = 1;
+  a.M = B * H * W; a.N = Cout; a.K = Cin;
+  a.out_sg = (long long)a.M * a.N;
+  a.st_mean = st_mean; a.st_m2 = st_m2; a.st_cnt = st_cnt;
+  a.st_nblk = stat_blocks(a.M);
+  a.ysh = y1_shift;
   a.rs = res; a.rs_sc = res_scale; a.rs_sh = res_shift; a.fout = out; a.fmask = out_mask;
   if (!conv_big16_fold_launch(dtype, a, stream)) return 1;
   return check_launch("conv2d_fwd_fold_h16");
@@ -610,30 +392,20 @@ MAUV_API int mauv_stem_fwd_h16(int dtype, const void* cols, const void* w, void*
   if (int e = check_shape16("stem_fwd_h16", dtype, G, 1, Kp, Cout, nullptr)) return e;
   if (M <= 0 || Kp % 64) { set_error("stem_fwd_h16: needs M > 0 and Kp % 64 == 0"); return kErrArg; }
   if (!aligned16(cols) || !aligned16(w)) { set_error("stem_fwd_h16: cols, w must be 16-B aligned"); return kErrArg; }
-  ConvArgs16 h = make_args16(1, 1, 1, M, Kp, G * Cout, 1, 1, 1, 0, nullptr);
-  h.x = (const u16*)cols; h.w = (const u16*)w; h.out = y;
-  h.M = M; h.N = G * Cout; h.K = Kp;
-  h.out_sg = (long long)M * Cout;
-  h.st_mean = st_mean; h.st_m2 = st_m2; h.st_cnt = st_cnt;
-  h.st_nblk = ceil_div(M, conv_tile_rows(M));
-  h.ysh = y_shift;
-  ConvArgs a = pipe_args(h);
+  // cols as one 1 x M image of Kp channels
+  ConvArgs a = make_args(1, 1, 1, M, Kp, G * Cout, 1, 1, 1, 0, nullptr);
+  a.x = (const float*)cols; a.w = (const float*)w; a.out = (float*)y;
+  a.M = M; a.N = G * Cout; a.K = Kp;
+  a.out_sg = (long long)M * Cout;
+  a.st_mean = st_mean; a.st_m2 = st_m2; a.st_cnt = st_cnt;
+  a.st_nblk = stat_blocks(M);
+  a.ysh = y_shift;
   a.cpg = Cout;
-  // the pipelined kernel reads cols by a buffer descriptor (31-bit byte offsets): rows beyond
-  // that (configs[4]'s 512 px sonar at B = 256: 16.8 M rows) go in chunks of whole 128-row
-  // tiles, each writing its rows of y and its statistics blocks (st_base)
-  const long long lim_rows = (0x7fff0000LL / 2 / Kp) / 128 * 128;
-  for (long long r0 = 0; r0 < M; r0 += lim_rows) {
-    ConvArgs c = a;
-    c.M = (int)(M - r0 < lim_rows ? M - r0 : lim_rows);
-    // cols as one 1 x M "image" of Kp channels (make_args16 above): the chunk is 1 x c.M
-    c.W = c.Wo = c.M;
-    c.xs_h = c.xs_b = (long long)c.M * Kp;
-    c.x = (const float*)((const u16*)cols + r0 * Kp);
-    c.out = (float*)((u16*)y + r0 * Cout);
-    c.st_base = (int)(r0 / 128);
-    if (!conv_pipe16_launch(FWD, dtype, c, stream)) { set_error("stem_fwd_h16: shape outside the pipelined kernel"); return kErrArg; }
-  }
+  // the pipelined kernel reads cols by a buffer descriptor: in row chunks (conv_stem_row_chunks)
+  const long long rows = conv_stem_row_chunks(a, 2, [&](const ConvArgs& c) {
+    return conv_pipe16_launch(FWD, dtype, c, stream);
+  });
+  if (rows != M) { set_error("stem_fwd_h16: shape outside the pipelined kernel"); return kErrArg; }
   return check_launch("stem_fwd_h16");
 }
 
@@ -673,43 +445,35 @@ MAUV_API int mauv_conv2d_bwd_data_bn_h16(int dtype, const void* dy, const void* 
     if (bn_relu && !bn_mask && !bn_out && (!bn_scale || !bn_shift)) { set_error("conv2d_bwd_data_bn_h16: relu mask needs mask, out or scale/shift"); return kErrArg; }
     if (!aligned16(bn_y) || !aligned16(bn_out)) { set_error("conv2d_bwd_data_bn_h16: y, out must be 16-B aligned"); return kErrArg; }
   }
-  ConvArgs16 a = make_args16(G, B, H, W, Cin, Cout, R, S, stride, pad, nullptr);
-  a.dy = (const u16*)dy; a.w = (const u16*)w; a.out = dx;
-  a.addend = (const u16*)addend; a.accumulate = accumulate;
+  ConvArgs a = make_args(G, B, H, W, Cin, Cout, R, S, stride, pad, nullptr);
+  a.dy = (const float*)dy; a.w = (const float*)w; a.out = (float*)dx;
+  a.addend = (const float*)addend; a.accumulate = accumulate;
+  a.add_mask = addend_mask;
   a.N = Cin;
   a.out_sg = (long long)B * H * W * Cin;
-  int bp_base = 0;
-  const int bp_nblk = bst ? mauv_conv2d_bwd_data_stat_blocks(G, B, H, W, Cin, Cout, R, S, stride, pad) : 0;
+  if (bst) {
+    a.bp_y = (const float*)bn_y; a.bp_out = (const float*)bn_out; a.bp_mask = bn_mask;
+    a.bp_sc = bn_scale; a.bp_sh = bn_shift; a.bp_mean = bn_mean; a.bp_invstd = bn_invstd;
+    a.bp_relu = bn_relu; a.bp_p1 = bn_p1; a.bp_p2 = bn_p2;
+    a.bp_nblk = mauv_conv2d_bwd_data_stat_blocks(G, B, H, W, Cin, Cout, R, S, stride, pad);
+  }
+  // one launch per output-parity class (stride^2 of them; 1 for stride 1)
   for (int ph = 0; ph < stride; ++ph)
     for (int pw = 0; pw < stride; ++pw) {
-      a.ph = ph; a.pw = pw;
-      a.Hc = (H - ph + stride - 1) / stride;
-      a.Wc = (W - pw + stride - 1) / stride;
-      a.r0 = (ph + pad) % stride;
-      a.s0 = (pw + pad) % stride;
-      a.nr = a.r0 < R ? (R - a.r0 + stride - 1) / stride : 0;
-      a.ns = a.s0 < S ? (S - a.s0 + stride - 1) / stride : 0;
-      a.M = B * a.Hc * a.Wc;
-      a.K = a.nr * a.ns * Cout;
+      conv_parity_class(a, ph, pw);
       if (a.M <= 0) continue;
       // a tapless class accumulating into dx adds nothing (stride-2 1x1 downsample: 3 of 4)
       if (a.K == 0 && accumulate && !addend) {
         if (bst) { set_error("conv2d_bwd_data_bn_h16: partials over a tapless accumulate class"); return kErrArg; }
         continue;
       }
-      ConvArgs p = pipe_args(a);
-      p.add_mask = addend_mask;
-      if (bst) {
-        p.bp_y = (const float*)bn_y; p.bp_out = (const float*)bn_out; p.bp_mask = bn_mask;
-        p.bp_sc = bn_scale; p.bp_sh = bn_shift; p.bp_mean = bn_mean; p.bp_invstd = bn_invstd;
-        p.bp_relu = bn_relu; p.bp_p1 = bn_p1; p.bp_p2 = bn_p2;
-        p.bp_nblk = bp_nblk; p.bp_base = bp_base;
-        bp_base += ceil_div(a.M, conv_tile_rows(a.M));
-        if (!conv_pipe16_launch(DGRAD, dtype, p, stream)) { set_error("conv2d_bwd_data_bn_h16: shape outside the pipelined kernel"); return kErrArg; }
-      } else if (!conv_pipe16_launch(DGRAD, dtype, p, stream)) {
+      if (!conv_pipe16_launch(DGRAD, dtype, a, stream)) {
+        // the register-staged kernel writes no partials and reads no addend mask
+        if (bst) { set_error("conv2d_bwd_data_bn_h16: shape outside the pipelined kernel"); return kErrArg; }
         if (addend_mask) { set_error("conv2d_bwd_data_bn_h16: addend_mask outside the pipelined kernel"); return kErrArg; }
-        dispatch16<H_DGRAD, true>(dtype, a, stream);
+        dispatch16<DGRAD, true>(dtype, a, stream);
       }
+      a.bp_base += stat_blocks(a.M);
     }
   return check_launch("conv2d_bwd_data_h16");
 }
@@ -720,15 +484,17 @@ MAUV_API int mauv_conv2d_bwd_weight_h16(int dtype, const void* x, const long lon
                                         int H, int W, int Cin, int Cout, int R, int S, int stride,
                                         int pad, hipStream_t stream) {
   if (int e = check_shape16("conv2d_bwd_weight_h16", dtype, G, B, Cin, Cout, x_strides)) return e;
-  ConvArgs16 a = make_args16(G, B, H, W, Cin, Cout, R, S, stride, pad, x_strides);
-  a.x = (const u16*)x; a.dy = (const u16*)dy; a.out = ws;
+  ConvArgs a = make_args(G, B, H, W, Cin, Cout, R, S, stride, pad, x_strides);
+  a.x = (const float*)x; a.dy = (const float*)dy; a.out = ws;
   a.xsc = x_scale; a.xsh = x_shift; a.xrelu = x_relu;
   a.M = Cout; a.N = R * S * Cin; a.K = B * a.Ho * a.Wo;
   a.splits = splits;
-  ConvArgs p = pipe_args(a);
-  p.kchunk = ((a.K + splits - 1) / splits + 63) / 64 * 64;  // the pipelined kernel's BK
-  a.kchunk = ((a.K + splits - 1) / splits + HBK - 1) / HBK * HBK;
-  if (!conv_pipe16_launch(WGRAD, dtype, p, stream)) dispatch16<H_WGRAD, false>(dtype, a, stream);
+  // whole tile depths per split-K slice: the pipelined kernel's 64, else HBK
+  a.kchunk = ((a.K + splits - 1) / splits + 63) / 64 * 64;
+  if (!conv_pipe16_launch(WGRAD, dtype, a, stream)) {
+    a.kchunk = ((a.K + splits - 1) / splits + HBK - 1) / HBK * HBK;
+    dispatch16<WGRAD, false>(dtype, a, stream);
+  }
   return check_launch("conv2d_bwd_weight_h16");
 }
 

@@ -413,13 +413,12 @@ static void pipe16_tiles(const ConvArgs& a, hipStream_t st) {
   // short-K kernels: forwards, and data gradients without the BN-partials epilogue (K = the
   // parity class's taps x Cout)
   constexpr bool SHORT_OK = (MODE == FWD || MODE == DGRAD) && !STEM;
-  constexpr bool use = true;
   if (bm == 64 && bn == 64) launch_pipe16<MODE, DT, 64, 64, XBN, STEM>(a, st);
   else if (bm == 64) launch_pipe16<MODE, DT, 64, 128, XBN, STEM>(a, st);
   else if (bn == 64) launch_pipe16<MODE, DT, 128, 64, XBN, STEM>(a, st);
-  else if (SHORT_OK && use && a.K == 64)
+  else if (SHORT_OK && a.K == 64)
     launch_pipe16<MODE, DT, 128, 128, XBN, STEM, SHORT_OK ? 1 : 0>(a, st);
-  else if (SHORT_OK && use && a.K > 0 && a.K <= kShortK)
+  else if (SHORT_OK && a.K > 0 && a.K <= kShortK)
     launch_pipe16<MODE, DT, 128, 128, XBN, STEM, SHORT_OK ? 2 : 0>(a, st);
   else launch_pipe16<MODE, DT, 128, 128, XBN, STEM>(a, st);
 }

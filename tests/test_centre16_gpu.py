@@ -11,7 +11,9 @@ acc_start16), so the stored values and the statistics partials are those of y - 
   to fp32 rounding; — inputs with a large channel mean, c near it — the reconstructed
   y = stored + c closer to float64 than the uncentred store, in BatchNorm's units (the point of
   the change); and every route that keeps the implicit GEMM's k order (all but the chunked
-  3x3 row image) BIT-identical to it with the same centre, outputs and statistics;
+  3x3 row image) BIT-identical to it with the same centre, outputs and statistics — the
+  register-staged fallback (conv_gemm16.hip, Cin % 64 != 0) against the pipelined kernel on the
+  same operands with Cin zero-padded per tap to the next multiple of 64;
 * mauv_bn_stats_finalize with y_shift on the centred partials: scale that of the uncentred
   finalize (to fp32 rounding of the merge), mean = the stored values' mean, shift such that stored * scale + shift =
   y * scale + shift_uncentred, the running statistics those of the true mean, and y_shift
@@ -40,6 +42,8 @@ ROUTES = [
     ("big16", 2, 2, 16, 512, 256, 1, 1, 0),     # 256-row LDS-DMA tiles
     ("expand16", 2, 4, 16, 128, 512, 1, 1, 0),  # weight-stationary K = 128
     ("expand16", 2, 4, 16, 256, 1024, 1, 1, 0),  # weight-stationary K = 256
+    ("gemm16", 2, 2, 9, 32, 128, 1, 1, 0),      # register-staged fallback: one 32-deep tile
+    ("gemm16", 2, 2, 8, 96, 64, 3, 1, 1),       # ... 3x3 over Cin = 96 (Cin % 64 != 0)
 ]
 ROUTE_SET = {
     "pipe16": dict(big16=0, expand16=0, haloc16=0, halo3=0),
@@ -47,6 +51,7 @@ ROUTE_SET = {
     "haloc16": dict(big16=0, expand16=0, haloc16=1, halo3=0),
     "big16": dict(big16=2, big16_min_k=512, expand16=0, haloc16=0, halo3=0),
     "expand16": dict(big16=0, expand16=2, haloc16=0, halo3=0),
+    "gemm16": dict(big16=0, expand16=0, haloc16=0, halo3=0),   # the shape selects the fallback
 }
 
 
@@ -132,11 +137,16 @@ def test_centred_store_every_forward_route(case, dt):
     # the same centre through the implicit GEMM: bit-identical where the route keeps its k order
     # (haloc16 runs 64-channel chunks outer, taps inner: fp32-summation close, checked above)
     if route not in ("pipe16", "haloc16"):
+        # the fallback's shapes are outside the pipelined kernel: it takes them with Cin
+        # zero-padded per tap to a multiple of 64 (zero products add exactly, and both kernels
+        # step k in order in groups of 16)
+        Cp = -(-Cin // 64) * 64 if route == "gemm16" else Cin
+        xp, wp = F.pad(xd, (0, Cp - Cin)), F.pad(wd, (0, Cp - Cin))
         prev = ops.set_route(**ROUTE_SET["pipe16"])
         try:
             yp = torch.full_like(y1, float("nan"))
-            sp = _stat_bufs(ops, G, B, H, Cin, Cout, R, st, pd)
-            ops.conv2d_fwd(xd, wd, yp, G, B, H, H, Cin, Cout, R, st, pd, stats=sp, ysh=c)
+            sp = _stat_bufs(ops, G, B, H, Cp, Cout, R, st, pd)
+            ops.conv2d_fwd(xp, wp, yp, G, B, H, H, Cp, Cout, R, st, pd, stats=sp, ysh=c)
             torch.cuda.synchronize()
         finally:
             ops.set_route(**prev)

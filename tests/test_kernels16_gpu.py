@@ -51,6 +51,8 @@ CASES = [
     (1, 3, 10, 256, 256, 1, 1, 0),
     (2, 3, 9, 128, 64, 1, 1, 0),    # dgrad over a single 64-deep stage: the one-stage kernel
     (2, 3, 9, 256, 128, 1, 1, 0),   # dgrad K = 128: the short-K sequential data gradient
+    (2, 2, 9, 64, 96, 3, 2, 1),     # Cout % 64 != 0: the pipelined DGRAD declines (stride-2
+                                    # parity classes + addend through the register-staged kernel)
 ]
 
 
@@ -81,6 +83,17 @@ def test_conv16_fwd_dgrad_wgrad(case, dt):
         ops.conv2d_bwd_data(dy.to(dev), w.to(dev), dx, G, B, H, H, Cin, Cout, R, st, pad,
                             addend=addend.to(dev))
         close(dx, torch.stack(dx_ref) + addend.double(), 4 * ULP[dt])
+        if Cout % 64:
+            # the register-staged fallback gives the pipelined kernel's bits: the same operands
+            # with Cout zero-padded to a multiple of 64 (zero products add exactly; both kernels
+            # step k in order in groups of 16)
+            Cp = -(-Cout // 64) * 64
+            dyp = F.pad(dy, (0, Cp - Cout)).to(dev)
+            wp = F.pad(w, (0, 0, 0, 0, 0, 0, 0, Cp - Cout)).to(dev)
+            dxp = torch.empty_like(dx)
+            ops.conv2d_bwd_data(dyp, wp, dxp, G, B, H, H, Cin, Cp, R, st, pad,
+                                addend=addend.to(dev))
+            assert torch.equal(dx, dxp)
     splits = ops.wgrad_splits(G, B, H, H, Cin, Cout, R, st, pad)
     ws = torch.empty(splits, G, Cout, R * R * Cin, device=dev)
     ops.conv2d_bwd_weight(x.to(dev), dy.to(dev), ws, splits, G, B, H, H, Cin, Cout, R, st, pad)
@@ -121,11 +134,11 @@ def test_conv16_stem_shared_padded_input(dt):
 
 @pytest.mark.parametrize("dt", DTYPES, ids=["bf16", "f16"])
 @pytest.mark.parametrize("Cout", [128, 256])
-@pytest.mark.parametrize("Cin,R", [(64, 3), (64, 1), (128, 1)])
+@pytest.mark.parametrize("Cin,R", [(64, 3), (64, 1), (128, 1), (96, 3)])
 def test_conv16_lazy_bn_input_and_stats(dt, Cout, Cin, R):
     """x' = relu(x*scale + shift) applied on load (FWD and WGRAD) + epilogue statistics
     (3x3: the two-stage pipeline; 1x1 over 64 / 128 channels: the one-stage and short-K
-    forward kernels)."""
+    forward kernels; Cin = 96: the register-staged fallback forward)."""
     from mauv import ops
     G, B, H = 2, 3, 8
     torch.manual_seed(3)
@@ -163,6 +176,24 @@ def test_conv16_lazy_bn_input_and_stats(dt, Cout, Cin, R):
             dy[g].permute(0, 3, 1, 2).double())
         dw.append(wg.grad.permute(0, 2, 3, 1))
     close(ws.sum(0).view(G, Cout, R, R, Cin), torch.stack(dw), 1e-3)
+
+
+@pytest.mark.parametrize("dt", DTYPES, ids=["bf16", "f16"])
+def test_conv16_wgrad_wide_row_fallback(dt):
+    """A weight gradient over rows wider than 4096 output pixels, which the pipelined kernel
+    declines (its 16-bit multiply-shift pixel division): the register-staged kernel's split-K
+    slabs, summed, against a float64 einsum on the same 16-bit operands."""
+    from mauv import ops
+    G, B, H, W, Cin, Cout = 1, 1, 1, 4104, 16, 24
+    torch.manual_seed(4)
+    x = torch.randn(G, B, H, W, Cin).to(dt)
+    dy = torch.randn(G, B, H, W, Cout).to(dt)
+    splits = ops.wgrad_splits(G, B, H, W, Cin, Cout, 1, 1, 0)
+    ws = torch.full((splits, G, Cout, Cin), float("nan"), device=dev)
+    ops.conv2d_bwd_weight(x.to(dev), dy.to(dev), ws, splits, G, B, H, W, Cin, Cout, 1, 1, 0)
+    ref = torch.einsum("gpn,gpc->gnc", dy.double().reshape(G, -1, Cout),
+                       x.double().reshape(G, -1, Cin))
+    close(ws.sum(0), ref, 1e-4)
 
 
 @pytest.mark.parametrize("dt", DTYPES, ids=["bf16", "f16"])
