@@ -454,6 +454,38 @@ int mauv_mc_mean_ce(const float* logits, const long long* labels, int G, int B, 
 int mauv_mc_mean_bwd(const float* dmean, const float* gloss, const float* mean,
                      const long long* labels, int G, int B, int C, float* dlogits,
                      hipStream_t stream);
+/* The same head under the criterion a training loop is handed (`criterion` of
+ * train_multimodal_model / train_unimodal_model): what
+ *   F.cross_entropy(logits.mean(0), labels, weight=class_weight, ignore_index=ignore_index,
+ *                   reduction=("mean", "sum")[reduction], label_smoothing=label_smoothing)
+ * and its autograd compute.  class_weight fp32 [C], null = all ones; reduction 0 = mean, 1 = sum.
+ * With lp = log_softmax(mean[b]), p = exp(lp), y = labels[b], w the weights, W = sum_c w[c] and
+ * an item counted iff y != ignore_index:
+ *   nll_b = -w[y] lp[y];  smooth_b = -sum_c w[c] lp[c];  D = sum over counted items of w[y]
+ *   (mean) or 1 (sum);  loss = (1 - eps) sum_b nll_b / D + (eps / C) sum_b smooth_b / D
+ *   dlogits[g][b][c] = gloss / D ((1 - eps) w[y] (p[c] - [c == y]) + (eps / C) (p[c] W - w[c])) / G
+ * mean and pred follow mauv_mc_mean_ce's rules (float64 sum over g rounded once, at every C).
+ * Every C in 1..4096 runs the many-class kernels, so the label rules hold at C <= 32 too: a
+ * label equal to ignore_index is ignored even when it is a valid class (its dlogits rows are
+ * zero); any other label outside [0, C) makes the loss and that item's dlogits rows NaN and
+ * adds nothing to D; no label indexes memory unchecked.  Sum order: per-item terms, their sums
+ * and D in float64 in a fixed order by one block, rounded to float once, no atomics: the same
+ * bits from run to run.  Mean reduction with no counted weight: D = 0 and the loss is NaN
+ * (0 / 0, as torch); sum reduction with no counted item: 0.  denom [1] receives D; the backward
+ * reads it as written and does not recompute it.  Non-finite logits or weights propagate into
+ * the loss.  With class_weight null, label_smoothing 0, ignore_index -100 and reduction 0 the
+ * forward gives mauv_mc_mean_ce's mean, loss and pred bit for bit at C > 32.
+ * label_smoothing outside [0, 1], a reduction other than 0 / 1 and C > 4096 are -1; B == 0 or
+ * G == 0 launches nothing and returns 0.  labels (then loss, denom are untouched) and pred
+ * nullable in the forward. */
+int mauv_mc_mean_ce_ex(const float* logits, const long long* labels, const float* class_weight,
+                       float label_smoothing, long long ignore_index, int reduction, int G, int B,
+                       int C, float* mean, float* loss, float* denom, long long* pred,
+                       hipStream_t stream);
+int mauv_mc_mean_bwd_ex(const float* gloss, const float* mean, const long long* labels,
+                        const float* class_weight, float label_smoothing, long long ignore_index,
+                        int reduction, const float* denom, int G, int B, int C, float* dlogits,
+                        hipStream_t stream);
 /* inference/predictors.py:65-84, train/multimodal.py:305-310, train/unimodal.py:298-308:
  * sufficient statistics sums[b] = {sum_g p (C), sum_g p^2 (C), sum_g H[p_g]} (float64,
  * all-reducible across MC-sharded ranks), then mean prob, unbiased variance (mean over

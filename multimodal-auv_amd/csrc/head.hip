@@ -237,13 +237,24 @@ __global__ __launch_bounds__(256) void mc_finalize_kernel(const double* __restri
 // item and walk its C logits, which fits C = 7; here lanes run along the class axis (coalesced
 // loads of logits[g][b][0..C)), a wave or a block owns an item, and the row maximum, the sum of
 // exponentials and the argmax are cross-lane reductions in a fixed order.  No float atomics:
-// every output is bit-reproducible from run to run.
+// every output is bit-reproducible from run to run.  mauv_mc_mean_ce_ex / _bwd_ex run these
+// kernels at every C from 1 (a wave holds a row of C <= 64 as well as one of 33).
 constexpr int kSmallClasses = 32;   // up to here: the one-thread-per-item kernels above
 constexpr int kMaxClasses = 4096;   // the bound mauv_confusion_update has
 // Labels of the many-class head: -100 (torch's ignore_index) leaves the item out of the loss sum
 // and of its divisor and zeroes its dlogits rows; any other label outside [0, C) makes the loss
 // (and the item's dlogits) NaN.  No label indexes memory unchecked.
 constexpr long long kIgnoreLabel = -100;
+// The criterion of the many-class cross-entropy (torch's CrossEntropyLoss arguments).  kPlainCe is
+// CrossEntropyLoss(): with it every expression below multiplies by exactly 1.0 or is skipped on a
+// block-uniform branch, so mauv_mc_mean_ce / _bwd keep their bits.
+struct CeCrit {
+  const float* weight;   // [C] class weights, null = all ones
+  float eps;             // label_smoothing in [0, 1]
+  int sum;               // reduction: 0 = mean (divisor: the counted labels' weights), 1 = sum
+  long long ignore;      // ignore_index: compared before the range check, so it may be a class
+};
+constexpr CeCrit kPlainCe = {nullptr, 0.f, 0, kIgnoreLabel};
 
 struct ArgBest {
   float v;
@@ -327,18 +338,23 @@ __global__ __launch_bounds__(256) void mc_mean_wide_kernel(const float* __restri
 
 // argmax and cross-entropy of the [B][C] mean: ONE block (the loss is one fixed-order sum), a
 // wave per item (items w, w + NW, ...) holding the row in registers (C <= 64 * KT, lane l owns
-// classes l + 64 k), per-item terms and their sum in float64, rounded to float once.
+// classes l + 64 k), per-item terms and their sum in float64, rounded to float once.  With
+// lp = log_softmax(row), y the label and w the class weights, a counted item (y != cr.ignore) adds
+//   nll = -w[y] lp[y],   smooth = -sum_c w[c] lp[c] (only when eps > 0),   D += w[y]
+// and loss = (1 - eps) nll / D + (eps / C) smooth / D with D = 1 for the sum reduction (torch
+// divides the two parts separately: no counted weight is 0 / 0 = NaN in both).  A label outside
+// [0, C) adds NaN to nll and nothing to D.  The weights are read in the row's lane pattern.
 template <int KT, int NT>
 __global__ __launch_bounds__(NT) void mc_ce_wide_kernel(const float* __restrict__ mean,
                                                           const long long* __restrict__ labels,
-                                                          int B, int C, float* __restrict__ loss,
+                                                          int B, int C, CeCrit cr,
+                                                          float* __restrict__ loss,
+                                                          float* __restrict__ denom,
                                                           long long* __restrict__ pred) {
   constexpr int NW = NT / 64;
-  __shared__ double sacc[NW];
-  __shared__ int scnt[NW];
+  __shared__ double sacc[3][NW];
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  double acc = 0.0;
-  int cnt = 0;
+  double nll = 0.0, smooth = 0.0, den = 0.0;
   for (int b = w; b < B; b += NW) {   // wave-uniform control flow throughout
     const float* row = mean + (long long)b * C;
     float x[KT];
@@ -352,43 +368,75 @@ __global__ __launch_bounds__(NT) void mc_ce_wide_kernel(const float* __restrict_
     if (pred && lane == 0) pred[b] = best.i;
     if (!labels) continue;
     const long long y = labels[b];
-    if (y == kIgnoreLabel) continue;
+    if (y == cr.ignore) continue;
     const float m = best.v;   // the maximum over the non-NaN entries (-inf if there is none)
     double se = 0.0;
 #pragma unroll
     for (int k = 0; k < KT; ++k) se += (double)expf(x[k] - m);
     se = wave_sum_d(se);
-    ++cnt;
-    if (y < 0 || y >= C) acc += (double)NAN;
-    else acc += log(se) - ((double)row[y] - (double)m);
+    const double lse = log(se);
+    if (y < 0 || y >= C) {
+      nll += (double)NAN;
+    } else {
+      const double wy = cr.weight ? (double)cr.weight[y] : 1.0;
+      nll += wy * (lse - ((double)row[y] - (double)m));
+      den += wy;
+    }
+    if (cr.eps > 0.f) {
+      // a rolled loop over the cache-resident row: the registers of x[] end with the loop above
+      double s = 0.0;
+#pragma unroll 2
+      for (int c = lane; c < C; c += 64)
+        s += (cr.weight ? (double)cr.weight[c] : 1.0) * (lse - ((double)row[c] - (double)m));
+      smooth += wave_sum_d(s);
+    }
   }
   if (!labels) return;
-  if (lane == 0) { sacc[w] = acc; scnt[w] = cnt; }
+  if (lane == 0) { sacc[0][w] = nll; sacc[1][w] = smooth; sacc[2][w] = den; }
   __syncthreads();
   if (threadIdx.x == 0) {
-    double a = sacc[0];
-    int n = scnt[0];
-    for (int i = 1; i < NW; ++i) { a += sacc[i]; n += scnt[i]; }
-    loss[0] = (float)(a / (double)n);   // no counted item: 0 / 0 = NaN, as torch
+    double a = sacc[0][0], s = sacc[1][0], d = sacc[2][0];
+    for (int i = 1; i < NW; ++i) { a += sacc[0][i]; s += sacc[1][i]; d += sacc[2][i]; }
+    if (cr.sum) d = 1.0;
+    a /= d;   // mean reduction, no counted weight: 0 / 0 = NaN, as torch
+    if (cr.eps > 0.f) a = (1.0 - (double)cr.eps) * a + ((double)cr.eps / (double)C) * (s / d);
+    loss[0] = (float)a;
+    if (denom) denom[0] = (float)d;
   }
 }
 
-// dlogits[g][b][c] = (dmean[b][c] or g_loss * (softmax(mean) - onehot) / n_counted) / G; block per
-// (item, g), the softmax normalisers recomputed per block from the cache-resident mean.
+// dlogits[g][b][c] = (dmean[b][c] or dloss/dmean[b][c]) / G; block per (item, g), the softmax
+// normalisers recomputed per block from the cache-resident mean.  With p = softmax(mean[b]),
+// W = sum_c w[c] (one block sum per launch, only when eps > 0) and D the forward's divisor
+// (`denom`; null: the number of counted labels, which is D of kPlainCe):
+//   dloss/dmean[b][c] = g_loss / D ((1 - eps) w[y] (p[c] - [c == y]) + (eps / C) (p[c] W - w[c]))
+// zero for an ignored item, NaN for a label outside [0, C).
 __global__ __launch_bounds__(256) void mc_mean_bwd_wide_kernel(const float* __restrict__ dmean,
                                                                const float* __restrict__ gloss,
                                                                const float* __restrict__ mean,
                                                                const long long* __restrict__ labels,
-                                                               int G, int B, int C,
+                                                               int G, int B, int C, CeCrit cr,
+                                                               const float* __restrict__ denom,
                                                                float* __restrict__ dlogits) {
   __shared__ float smax[1][4], ssum[1][4];
   __shared__ int scnt[1][4];
+  __shared__ double swsum[1][4];
   const float fG = (float)G;
   int counted[1] = {0};
-  if (labels) {
-    for (int b = threadIdx.x; b < B; b += 256) counted[0] += labels[b] != kIgnoreLabel;
+  if (labels && !denom) {
+    for (int b = threadIdx.x; b < B; b += 256) counted[0] += labels[b] != cr.ignore;
     block_sum_u<4, 1, int>(counted, scnt);
   }
+  const bool smoothed = labels && cr.eps > 0.f;
+  float W = (float)C;
+  if (smoothed && cr.weight) {
+    double ws[1] = {0.0};
+    for (int c = threadIdx.x; c < C; c += 256) ws[0] += (double)cr.weight[c];
+    block_sum_u<4, 1, double>(ws, swsum);
+    W = (float)ws[0];
+  }
+  const float D = !labels ? 1.f : denom ? denom[0] : (float)counted[0];
+  const float se_c = cr.eps / (float)C;
   for (int b = blockIdx.x; b < B; b += gridDim.x) {   // block-uniform control flow throughout
     for (int g = blockIdx.y; g < G; g += gridDim.y) {
       float* out = dlogits + ((long long)g * B + b) * C;
@@ -398,7 +446,7 @@ __global__ __launch_bounds__(256) void mc_mean_bwd_wide_kernel(const float* __re
         continue;
       }
       const long long y = labels[b];
-      if (y == kIgnoreLabel) {
+      if (y == cr.ignore) {
         for (int c = threadIdx.x; c < C; c += 256) out[c] = 0.f;
         continue;
       }
@@ -409,10 +457,14 @@ __global__ __launch_bounds__(256) void mc_mean_bwd_wide_kernel(const float* __re
       float se[1] = {0.f};
       for (int c = threadIdx.x; c < C; c += 256) se[0] += expf(x[c] - m[0]);
       block_sum_u<4, 1, float>(se, ssum);
-      const float k = (y < 0 || y >= C) ? NAN : (gloss ? gloss[0] : 1.0f) / (float)counted[0];
+      const bool bad = y < 0 || y >= C;
+      const float k = bad ? NAN : (gloss ? gloss[0] : 1.0f) / D;
+      const float a = (1.f - cr.eps) * (cr.weight && !bad ? cr.weight[y] : 1.f);
       for (int c = threadIdx.x; c < C; c += 256) {
         const float p = expf(x[c] - m[0]) / se[0];
-        out[c] = k * (p - (y == c ? 1.f : 0.f)) / fG;
+        float t = a * (p - (y == c ? 1.f : 0.f));
+        if (smoothed) t += se_c * (p * W - (cr.weight ? cr.weight[c] : 1.f));
+        out[c] = k * t / fG;
       }
     }
   }
@@ -625,10 +677,23 @@ static int item_grid(int B, int cap) { return B < cap ? B : cap; }
 
 template <int KT>
 static void launch_mc_ce_wide(const float* mean, const long long* labels, int B, int C,
-                              float* loss, long long* pred, hipStream_t stream) {
+                              const CeCrit& cr, float* loss, float* denom, long long* pred,
+                              hipStream_t stream) {
   // 64 row registers per lane (C > 2048) fit without scratch under the 512-thread budget only
   constexpr int NT = KT > 32 ? 512 : 1024;
-  hipLaunchKernelGGL((mc_ce_wide_kernel<KT, NT>), dim3(1), dim3(NT), 0, stream, mean, labels, B, C, loss, pred);
+  hipLaunchKernelGGL((mc_ce_wide_kernel<KT, NT>), dim3(1), dim3(NT), 0, stream, mean, labels, B, C, cr, loss, denom, pred);
+}
+// the register tier of the row: 64 * KT classes, down to C = 1 on KT = 1
+static void launch_mc_ce(const float* mean, const long long* labels, int B, int C,
+                         const CeCrit& cr, float* loss, float* denom, long long* pred,
+                         hipStream_t stream) {
+  if (C <= 64) launch_mc_ce_wide<1>(mean, labels, B, C, cr, loss, denom, pred, stream);
+  else if (C <= 128) launch_mc_ce_wide<2>(mean, labels, B, C, cr, loss, denom, pred, stream);
+  else if (C <= 256) launch_mc_ce_wide<4>(mean, labels, B, C, cr, loss, denom, pred, stream);
+  else if (C <= 512) launch_mc_ce_wide<8>(mean, labels, B, C, cr, loss, denom, pred, stream);
+  else if (C <= 1024) launch_mc_ce_wide<16>(mean, labels, B, C, cr, loss, denom, pred, stream);
+  else if (C <= 2048) launch_mc_ce_wide<32>(mean, labels, B, C, cr, loss, denom, pred, stream);
+  else launch_mc_ce_wide<64>(mean, labels, B, C, cr, loss, denom, pred, stream);
 }
 template <int NT, int KT, int U>
 static void launch_mc_stats_wide(const float* logits, int G, int B, int C, float eps_h,
@@ -649,15 +714,7 @@ MAUV_API int mauv_mc_mean_ce(const float* logits, const long long* labels, int G
   }
   const long long BC = (long long)B * C;
   hipLaunchKernelGGL(mc_mean_wide_kernel, dim3(grid1(BC)), dim3(256), 0, stream, logits, G, BC, mean);
-  if (labels || pred) {
-    if (C <= 64) launch_mc_ce_wide<1>(mean, labels, B, C, loss, pred, stream);
-    else if (C <= 128) launch_mc_ce_wide<2>(mean, labels, B, C, loss, pred, stream);
-    else if (C <= 256) launch_mc_ce_wide<4>(mean, labels, B, C, loss, pred, stream);
-    else if (C <= 512) launch_mc_ce_wide<8>(mean, labels, B, C, loss, pred, stream);
-    else if (C <= 1024) launch_mc_ce_wide<16>(mean, labels, B, C, loss, pred, stream);
-    else if (C <= 2048) launch_mc_ce_wide<32>(mean, labels, B, C, loss, pred, stream);
-    else launch_mc_ce_wide<64>(mean, labels, B, C, loss, pred, stream);
-  }
+  if (labels || pred) launch_mc_ce(mean, labels, B, C, kPlainCe, loss, nullptr, pred, stream);
   return check_launch("mc_mean_ce");
 }
 MAUV_API int mauv_mc_mean_bwd(const float* dmean, const float* gloss, const float* mean,
@@ -668,8 +725,42 @@ MAUV_API int mauv_mc_mean_bwd(const float* dmean, const float* gloss, const floa
   if (C <= kSmallClasses)
     hipLaunchKernelGGL(mc_mean_bwd_kernel, dim3(grid1(B)), dim3(256), 0, stream, dmean, gloss, mean, labels, G, B, C, dlogits);
   else
-    hipLaunchKernelGGL(mc_mean_bwd_wide_kernel, dim3(item_grid(B, 256), item_grid(G, 64)), dim3(256), 0, stream, dmean, gloss, mean, labels, G, B, C, dlogits);
+    hipLaunchKernelGGL(mc_mean_bwd_wide_kernel, dim3(item_grid(B, 256), item_grid(G, 64)), dim3(256), 0, stream, dmean, gloss, mean, labels, G, B, C, kPlainCe, nullptr, dlogits);
   return check_launch("mc_mean_bwd");
+}
+// The same head under CrossEntropyLoss(weight, ignore_index, reduction, label_smoothing): the
+// many-class kernels at every C (no label indexes memory unchecked, C <= 32 included).
+static bool ce_crit_ok(const char* what, float eps, int reduction) {
+  if (!(eps >= 0.f && eps <= 1.f) || (reduction != 0 && reduction != 1)) {
+    set_error(std::string(what) + ": label_smoothing must be in [0, 1] and reduction 0 (mean) or 1 (sum)");
+    return false;
+  }
+  return true;
+}
+MAUV_API int mauv_mc_mean_ce_ex(const float* logits, const long long* labels,
+                                const float* class_weight, float label_smoothing,
+                                long long ignore_index, int reduction, int G, int B, int C,
+                                float* mean, float* loss, float* denom, long long* pred,
+                                hipStream_t stream) {
+  if (!mc_args_ok("mc_mean_ce_ex", G, B, C) || !ce_crit_ok("mc_mean_ce_ex", label_smoothing, reduction))
+    return kErrArg;
+  if (B == 0 || G == 0) return 0;
+  const long long BC = (long long)B * C;
+  hipLaunchKernelGGL(mc_mean_wide_kernel, dim3(grid1(BC)), dim3(256), 0, stream, logits, G, BC, mean);
+  const CeCrit cr = {class_weight, label_smoothing, reduction, ignore_index};
+  if (labels || pred) launch_mc_ce(mean, labels, B, C, cr, loss, denom, pred, stream);
+  return check_launch("mc_mean_ce_ex");
+}
+MAUV_API int mauv_mc_mean_bwd_ex(const float* gloss, const float* mean, const long long* labels,
+                                 const float* class_weight, float label_smoothing,
+                                 long long ignore_index, int reduction, const float* denom,
+                                 int G, int B, int C, float* dlogits, hipStream_t stream) {
+  if (!mc_args_ok("mc_mean_bwd_ex", G, B, C) || !ce_crit_ok("mc_mean_bwd_ex", label_smoothing, reduction))
+    return kErrArg;
+  if (B == 0 || G == 0) return 0;
+  const CeCrit cr = {class_weight, label_smoothing, reduction, ignore_index};
+  hipLaunchKernelGGL(mc_mean_bwd_wide_kernel, dim3(item_grid(B, 256), item_grid(G, 64)), dim3(256), 0, stream, (const float*)nullptr, gloss, mean, labels, G, B, C, cr, denom, dlogits);
+  return check_launch("mc_mean_bwd_ex");
 }
 MAUV_API int mauv_mc_stats(const float* logits, int G, int B, int C, float eps_h, double* sums,
                            int accumulate, hipStream_t stream) {

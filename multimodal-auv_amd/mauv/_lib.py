@@ -91,6 +91,8 @@ SIGNATURES = {
     "mauv_colsum": [P, I, I, I, P, I, P],
     "mauv_mc_mean_ce": [P, P, I, I, I, P, P, P, P],
     "mauv_mc_mean_bwd": [P, P, P, P, I, I, I, P, P],
+    "mauv_mc_mean_ce_ex": [P, P, P, F, LL, I, I, I, I, P, P, P, P, P],
+    "mauv_mc_mean_bwd_ex": [P, P, P, P, F, LL, I, P, I, I, I, P, P],
     "mauv_mc_stats": [P, I, I, I, F, P, I, P],
     "mauv_mc_finalize": [P, I, I, I, F, P, P, P, P, P, P],
     "mauv_nonfinite_count": [P, LL, P, P],

@@ -31,6 +31,33 @@ class _MCMeanCE(torch.autograd.Function):
         return dl, None
 
 
+class _MCMeanCEEx(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, labels, weight, label_smoothing, ignore_index, reduction):
+        G, B, C = logits.shape
+        mean = torch.empty(B, C, device=logits.device)
+        loss = torch.empty(1, device=logits.device)
+        denom = torch.empty(1, device=logits.device)
+        pred = torch.empty(B, dtype=torch.int64, device=logits.device)
+        ops.mc_mean_ce_ex(logits, labels, weight, label_smoothing, ignore_index, reduction,
+                          G, B, C, mean, loss, denom, pred)
+        ctx.save_for_backward(mean, labels, weight, denom)
+        ctx.G = G
+        ctx.crit = (label_smoothing, ignore_index, reduction)
+        ctx.mark_non_differentiable(mean, pred)
+        return loss[0], mean, pred
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gloss, gmean, gpred):
+        mean, labels, weight, denom = ctx.saved_tensors
+        B, C = mean.shape
+        dl = torch.empty(ctx.G, B, C, device=mean.device)
+        ops.mc_mean_bwd_ex(gloss.reshape(1).float().contiguous(), mean, labels, weight,
+                           *ctx.crit, denom, ctx.G, B, C, dl)
+        return dl, None, None, None, None, None
+
+
 class _MCMean(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits):
@@ -52,6 +79,18 @@ class _MCMean(torch.autograd.Function):
 def mc_mean_ce(logits, labels):
     """-> (cross-entropy of the MC-mean logits [0-d], mean logits [B,C], argmax [B])."""
     return _MCMeanCE.apply(logits.contiguous(), labels.long().contiguous())
+
+
+def mc_mean_ce_ex(logits, labels, weight=None, label_smoothing=0.0, ignore_index=-100,
+                  reduction="mean"):
+    """``mc_mean_ce`` under ``CrossEntropyLoss(weight, ignore_index=..., reduction=...,
+    label_smoothing=...)`` (reduction "mean" or "sum"), on the many-class kernels at every C: a
+    label equal to ``ignore_index`` is left out, any other label outside [0, C) gives a NaN
+    loss (include/mauv.h).  -> (loss [0-d], mean logits [B,C], argmax [B])."""
+    if reduction not in ops.MC_REDUCTIONS:
+        raise ValueError(f"reduction must be 'mean' or 'sum', got {reduction!r}")
+    return _MCMeanCEEx.apply(logits.contiguous(), labels.long().contiguous(), weight,
+                             float(label_smoothing), int(ignore_index), reduction)
 
 
 def mc_mean(logits):

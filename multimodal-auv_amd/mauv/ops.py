@@ -714,6 +714,38 @@ def mc_mean_bwd(dmean, gloss, mean, labels, G, B, C, dlogits):
                                _p(dlogits), stream()), "mc_mean_bwd")
 
 
+MC_REDUCTIONS = {"mean": 0, "sum": 1}   # include/mauv.h: mauv_mc_mean_ce_ex's `reduction`
+
+
+def _mc_weight(weight, C):
+    _dev(torch.float32, weight)
+    if weight is not None and weight.numel() != C:
+        raise ValueError(f"class weights must have C={C} elements, got {weight.numel()}")
+
+
+def mc_mean_ce_ex(logits, labels, weight, label_smoothing, ignore_index, reduction, G, B, C,
+                  mean, loss, denom, pred=None):
+    """``reduction``: "mean" or "sum"; ``weight`` None = all ones."""
+    _mc_classes(C)
+    _dev(torch.float32, logits, mean, loss, denom)
+    _dev(torch.int64, labels, pred)
+    _mc_weight(weight, C)
+    check(lib.mauv_mc_mean_ce_ex(_p(logits), _p(labels), _p(weight), label_smoothing,
+                                 ignore_index, MC_REDUCTIONS[reduction], G, B, C, _p(mean),
+                                 _p(loss), _p(denom), _p(pred), stream()), "mc_mean_ce_ex")
+
+
+def mc_mean_bwd_ex(gloss, mean, labels, weight, label_smoothing, ignore_index, reduction, denom,
+                   G, B, C, dlogits):
+    _mc_classes(C)
+    _dev(torch.float32, gloss, mean, denom, dlogits)
+    _dev(torch.int64, labels)
+    _mc_weight(weight, C)
+    check(lib.mauv_mc_mean_bwd_ex(_p(gloss), _p(mean), _p(labels), _p(weight), label_smoothing,
+                                  ignore_index, MC_REDUCTIONS[reduction], _p(denom), G, B, C,
+                                  _p(dlogits), stream()), "mc_mean_bwd_ex")
+
+
 def mc_stats(logits, G, B, C, eps_h, sums, accumulate=False):
     _mc_classes(C)
     _dev(torch.float32, logits)

@@ -38,6 +38,41 @@ def _is_plain_ce(criterion):
             and float(getattr(criterion, "label_smoothing", 0.0)) == 0.0)
 
 
+_INT_LABELS = (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8)
+
+
+def _ce_spec(criterion, logits, labels):
+    """The keywords of ``mchead.mc_mean_ce_ex`` for a criterion the fused head computes, else
+    None (the caller then applies the criterion itself): exactly ``nn.CrossEntropyLoss`` with
+    mean or sum reduction, no weight or contiguous fp32 weights of C elements on the logits'
+    device, and 1-D integer class labels (class-probability targets are not fused)."""
+    if type(criterion) is not nn.CrossEntropyLoss or criterion.reduction not in ("mean", "sum"):
+        return None
+    w = criterion.weight
+    if w is not None and not (w.dtype == torch.float32 and w.dim() == 1 and w.is_contiguous()
+                              and w.numel() == logits.shape[-1] and w.device == logits.device):
+        return None
+    if labels.dim() != 1 or labels.dtype not in _INT_LABELS:
+        return None
+    eps = float(getattr(criterion, "label_smoothing", 0.0))
+    if not 0.0 <= eps <= 1.0:
+        return None
+    return dict(weight=w, label_smoothing=eps, ignore_index=int(criterion.ignore_index),
+                reduction=criterion.reduction)
+
+
+def _fused_ce(criterion, logits, labels):
+    """(ce, output_mean, predicted) of ROCm logits on the fused head, or None: the plain
+    criterion on ``mc_mean_ce`` (its bits as ever), any other ``_ce_spec`` admits on
+    ``mc_mean_ce_ex``.  None: the caller applies the criterion to the mean itself."""
+    if not logits.is_cuda:
+        return None
+    if _is_plain_ce(criterion):
+        return mchead.mc_mean_ce(logits, labels)
+    spec = _ce_spec(criterion, logits, labels)
+    return None if spec is None else mchead.mc_mean_ce_ex(logits, labels, **spec)
+
+
 def mc_logits(model, num_mc, *inputs):
     """[num_mc, B, C]: batched on mauv models, the reference's sequential loop otherwise."""
     core = unwrap(model)
@@ -95,8 +130,9 @@ def mc_loss(model, inputs_tuple, labels, criterion, num_mc, batch_size, kl_w):
     """Forward part of one training batch -> (loss, output_mean, predicted, ce, scaled_kl)."""
     logits = mc_logits(model, num_mc, *inputs_tuple)
     kl = get_kl_loss(model)
-    if _is_plain_ce(criterion) and logits.is_cuda:
-        ce, output, predicted = mchead.mc_mean_ce(logits, labels)
+    fused = _fused_ce(criterion, logits, labels)
+    if fused is not None:
+        ce, output, predicted = fused
     else:
         output = mchead.mc_mean(logits) if logits.is_cuda else logits.mean(0)
         ce = criterion(output, labels)
@@ -534,8 +570,9 @@ def train_unimodal_model(model, dataloader, criterion, optimizer, epoch, total_n
                 optimizer.zero_grad()
                 logits = mc_logits(model, num_mc, x)
                 kl = get_kl_loss(model)
-                if _is_plain_ce(criterion) and logits.is_cuda:
-                    ce, output, predicted = mchead.mc_mean_ce(logits, labels)
+                fused = _fused_ce(criterion, logits, labels)
+                if fused is not None:
+                    ce, output, predicted = fused
                 else:
                     output = mchead.mc_mean(logits) if logits.is_cuda else logits.mean(0)
                     ce = criterion(output, labels)
