@@ -310,55 +310,60 @@ int mauv_bn_stats_finalize(int G, int nblk, int C, const float* pmean, const flo
                            float* run_mean, float* run_var, float momentum, float eps,
                            float* workspace, float* mean, float* invstd, float* scale,
                            float* shift, const float* y_shift, hipStream_t stream);
-/* out = [relu](y*scale + shift (+ res')); res' = res*res_scale + res_shift when res_scale is
- * non-NULL — the bottleneck's downsample BatchNorm applied inside the residual add (its output
- * is never materialised). */
+/* The forward apply, one implementation behind three entries:
+ *   out = [relu](y*scale + shift (+ res')); res' = res*res_scale + res_shift when res_scale is
+ *   non-NULL — the bottleneck's downsample BatchNorm applied inside the residual add (its output
+ *   is never materialised); C % 8 == 0.
+ * mauv_bn_apply_mask is the full form (dtype -1 = fp32, 0 = bf16, 1 = f16: the type of
+ * y/res/out; scale/shift always fp32) with relu fixed to 1: it also writes the ReLU mask bits of
+ * the stored output, mask[G][M][C/8] (bit e of byte j: out[8j+e] > 0, non-NULL), which the
+ * backward reads instead of the 2-4 B output; C <= 2048.  It replaces the torchvision Bottleneck
+ * bn3 -> += identity -> relu.  mauv_bn_apply is that form with dtype -1, relu free and no mask
+ * (any C % 8 == 0), mauv_bn_apply_h16 the same with dtype 0 or 1: the same `out` bits. */
 int mauv_bn_apply(const float* y, const float* scale, const float* shift, const float* res,
                   const float* res_scale, const float* res_shift, int relu, float* out, int G,
                   long long M, int C, hipStream_t stream);
-int mauv_bn_eval_params(int G, int C, const float* gamma, const float* beta,
-                        const float* run_mean, const float* run_var, float eps, float* scale,
-                        float* shift, hipStream_t stream);
-/* out NULL + relu: the mask is recomputed as y*scale + shift > 0 (lazily-applied BN).
- * pre_p1/pre_p2 (nullable): partial sums already produced by a dgrad epilogue
- * ([G][pre_nblk][C]) — the partial pass over dout is skipped. */
-int mauv_bn_bwd(const float* y, const float* out, const float* dout, int relu,
-                const float* mean, const float* invstd, const float* scale, const float* shift,
-                int G, long long M, int C, float* workspace, float* dy, float* dres,
-                float* dgamma, float* dbeta, const float* pre_p1, const float* pre_p2,
-                int pre_nblk, hipStream_t stream);
-/* 16-bit activations (dtype 0 = bf16, 1 = f16): y/res/out/dout/dy/dres are 16-bit words;
- * statistics, scale/shift, workspace and dgamma/dbeta fp32 (same maths as above). */
 int mauv_bn_apply_h16(int dtype, const void* y, const float* scale, const float* shift,
                       const void* res, const float* res_scale, const float* res_shift, int relu,
                       void* out, int G, long long M, int C, hipStream_t stream);
-int mauv_bn_bwd_h16(int dtype, const void* y, const void* out, const void* dout, int relu,
-                    const float* mean, const float* invstd, const float* scale,
-                    const float* shift, int G, long long M, int C, float* workspace, void* dy,
-                    void* dres, float* dgamma, float* dbeta, hipStream_t stream);
-
-/* Block-output BN apply (+ReLU, +residual as mauv_bn_apply) that also writes the ReLU mask
- * bits of the stored output, mask[G][M][C/8] (bit e of byte j: out[8j+e] > 0), and the
- * BN + ReLU backward that reads them instead of the output (dres = dz as in mauv_bn_bwd).
- * dtype -1 = fp32, 0 = bf16, 1 = f16; C % 8 == 0, C <= 2048.  Same results as
- * mauv_bn_apply / mauv_bn_bwd with `out`; replaces the same torchvision Bottleneck
- * bn3 -> += identity -> relu (and its autograd) as they do. */
 int mauv_bn_apply_mask(int dtype, const void* y, const float* scale, const float* shift,
                        const void* res, const float* res_scale, const float* res_shift, void* out,
                        unsigned char* mask, int G, long long M, int C, hipStream_t stream);
-int mauv_bn_bwd_mask(int dtype, const void* y, const unsigned char* mask, const void* dout,
-                     const float* mean, const float* invstd, const float* scale, int G,
-                     long long M, int C, float* workspace, void* dy, void* dres, float* dgamma,
-                     float* dbeta, hipStream_t stream);
-/* Every form above in one entry (dtype -1 fp32, 0 bf16, 1 f16): ReLU mask from mask bits, else
- * out, else y*scale+shift; pre_p1/pre_p2/pre_nblk (nullable): partial sums a data-gradient
- * epilogue already wrote (mauv_conv2d_bwd_data_bn_h16 / _f32), so only the finalize and the
- * apply pass run.  dy and dres both NULL: partials / parameter gradients only. */
+int mauv_bn_eval_params(int G, int C, const float* gamma, const float* beta,
+                        const float* run_mean, const float* run_var, float eps, float* scale,
+                        float* shift, hipStream_t stream);
+/* The backward, defined by mauv_bn_bwd_ex (dtype -1 = fp32, 0 = bf16, 1 = f16: the type of
+ * y/out/dout/dy/dres; statistics, scale/shift, workspace and dgamma/dbeta always fp32):
+ *   dz = dout where the ReLU passed: by the mask bits of mauv_bn_apply_mask when mask is
+ *        non-NULL (relu and out are then ignored), else all of dout when relu is 0, else where
+ *        out > 0, else (out NULL: lazily-applied BN) where y*scale + shift > 0,
+ *   dy = gamma*invstd*(dz - mean(dz) - xhat*mean(dz*xhat)),  dres = dz (nullable),
+ *   dgamma += sum dz*xhat, dbeta += sum dz (over all groups; nullable).
+ * pre_p1/pre_p2 (nullable, [G][pre_nblk][C]): the partial sums of dz and dz*xhat a data-gradient
+ * epilogue already wrote (mauv_conv2d_bwd_data_bn_h16 / _f32): the partial pass over dout is
+ * skipped, only the finalize and the apply pass run.  dy and dres both NULL: partials /
+ * parameter gradients only.  C % 8 == 0, C <= 2048; workspace: mauv_bn_workspace_floats. */
 int mauv_bn_bwd_ex(int dtype, const void* y, const void* out, const unsigned char* mask,
                    const void* dout, int relu, const float* mean, const float* invstd,
                    const float* scale, const float* shift, int G, long long M, int C,
                    float* workspace, void* dy, void* dres, float* dgamma, float* dbeta,
                    const float* pre_p1, const float* pre_p2, int pre_nblk, hipStream_t stream);
+/* mauv_bn_bwd_ex with dtype = -1 and mask = NULL. */
+int mauv_bn_bwd(const float* y, const float* out, const float* dout, int relu,
+                const float* mean, const float* invstd, const float* scale, const float* shift,
+                int G, long long M, int C, float* workspace, float* dy, float* dres,
+                float* dgamma, float* dbeta, const float* pre_p1, const float* pre_p2,
+                int pre_nblk, hipStream_t stream);
+/* mauv_bn_bwd_ex with dtype 0 or 1, mask = NULL and no pre_p1/pre_p2. */
+int mauv_bn_bwd_h16(int dtype, const void* y, const void* out, const void* dout, int relu,
+                    const float* mean, const float* invstd, const float* scale,
+                    const float* shift, int G, long long M, int C, float* workspace, void* dy,
+                    void* dres, float* dgamma, float* dbeta, hipStream_t stream);
+/* mauv_bn_bwd_ex with a non-NULL mask, out = shift = NULL and no pre_p1/pre_p2. */
+int mauv_bn_bwd_mask(int dtype, const void* y, const unsigned char* mask, const void* dout,
+                     const float* mean, const float* invstd, const float* scale, int G,
+                     long long M, int C, float* workspace, void* dy, void* dres, float* dgamma,
+                     float* dbeta, hipStream_t stream);
 
 /* ---- pooling (pool.hip): torchvision stem maxpool 3x3/2 pad 1 and adaptive avgpool ------ */
 /* max-pool forward: C % 8 == 0 (the stem: 64); backward: C % 4 == 0. */

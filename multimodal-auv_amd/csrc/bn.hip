@@ -22,14 +22,6 @@ namespace mauv {
 struct RowMap {
   int tpr, rp, cpt;  // threads per row (float4 each), rows in parallel, float4 per thread
 };
-static inline RowMap row_map(int C) {
-  RowMap r;
-  const int c4 = C / 4;
-  r.tpr = c4 < 256 ? c4 : 256;
-  r.rp = 256 / r.tpr;
-  r.cpt = c4 / r.tpr;
-  return r;
-}
 
 constexpr int MAXCPT = 2;  // C <= 2048
 
@@ -143,6 +135,40 @@ __device__ __forceinline__ double lane_sum16(double v, double (*red)[64], int tx
   return s;
 }
 
+// The two passes of the exact merge of partials [b0, b1) of channel c of group g by a block's
+// 16 lanes of that channel: lane ty takes every FIN_L-th partial, lane_sum16 adds the lanes in
+// order.  Pass 1 returns N = sum n_b and leaves this lane's part of sum n_b*mean_b in s (the
+// caller sums the lanes and divides: only a segment can be without rows); pass 2 returns
+// sum [M2_b + n_b*(mean_b - mu)^2].
+__device__ __forceinline__ double merge_counts(int g, int c, int C, int nblk, int b0, int b1,
+                                               const float* pmean, const float* pcnt,
+                                               double (*red)[64], int tx, int ty, double& s) {
+  double n = 0.0;
+  s = 0.0;
+  if (c < C) {
+    for (int b = b0 + ty; b < b1; b += FIN_L) {
+      const double nb = pcnt[(long long)g * nblk + b];
+      n += nb;
+      s += nb * (double)pmean[((long long)g * nblk + b) * C + c];
+    }
+  }
+  return lane_sum16(n, red, tx, ty);
+}
+__device__ __forceinline__ double merge_m2(int g, int c, int C, int nblk, int b0, int b1,
+                                           double mu, const float* pmean, const float* pm2,
+                                           const float* pcnt, double (*red)[64], int tx,
+                                           int ty) {
+  double q = 0.0;
+  if (c < C) {
+    for (int b = b0 + ty; b < b1; b += FIN_L) {
+      const long long o = ((long long)g * nblk + b) * C + c;
+      const double d = (double)pmean[o] - mu;
+      q += (double)pm2[o] + pcnt[(long long)g * nblk + b] * d * d;
+    }
+  }
+  return lane_sum16(q, red, tx, ty);
+}
+
 __global__ __launch_bounds__(1024) void bn_stats_final(
     int G, int nblk, int C, const float* __restrict__ pmean, const float* __restrict__ pm2,
     const float* __restrict__ pcnt, const float* __restrict__ gamma,
@@ -152,25 +178,10 @@ __global__ __launch_bounds__(1024) void bn_stats_final(
   const int g = blockIdx.y, tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
   const int c = blockIdx.x * 64 + tx;
   __shared__ double red[FIN_L][64];
-  double n = 0.0, s = 0.0;
-  if (c < C) {
-    for (int b = ty; b < nblk; b += FIN_L) {
-      const double nb = pcnt[(long long)g * nblk + b];
-      n += nb;
-      s += nb * (double)pmean[((long long)g * nblk + b) * C + c];
-    }
-  }
-  const double nn = lane_sum16(n, red, tx, ty);
+  double s;
+  const double nn = merge_counts(g, c, C, nblk, 0, nblk, pmean, pcnt, red, tx, ty, s);
   const double mu = lane_sum16(s, red, tx, ty) / nn;
-  double q = 0.0;
-  if (c < C) {
-    for (int b = ty; b < nblk; b += FIN_L) {
-      const long long o = ((long long)g * nblk + b) * C + c;
-      const double d = (double)pmean[o] - mu;
-      q += (double)pm2[o] + pcnt[(long long)g * nblk + b] * d * d;
-    }
-  }
-  const double mm = lane_sum16(q, red, tx, ty);
+  const double mm = merge_m2(g, c, C, nblk, 0, nblk, mu, pmean, pm2, pcnt, red, tx, ty);
   if (ty != 0 || c >= C) return;
   stats_out(G, g, c, C, nn, mu, mm, gamma, beta, eps, ysh, mean_out, invstd_out, scale_out,
             shift_out, uvar_out);
@@ -200,25 +211,10 @@ __global__ __launch_bounds__(1024) void bn_stats_seg(int nblk, int C, int SEG,
   const int c = blockIdx.x * 64 + tx;
   const int b0 = sg * SEG, b1 = min(nblk, b0 + SEG);
   __shared__ double red[FIN_L][64];
-  double n = 0.0, s = 0.0;
-  if (c < C) {
-    for (int b = b0 + ty; b < b1; b += FIN_L) {
-      const double nb = pcnt[(long long)g * nblk + b];
-      n += nb;
-      s += nb * (double)pmean[((long long)g * nblk + b) * C + c];
-    }
-  }
-  const double nn = lane_sum16(n, red, tx, ty);
+  double s;
+  const double nn = merge_counts(g, c, C, nblk, b0, b1, pmean, pcnt, red, tx, ty, s);
   const double mu = nn > 0.0 ? lane_sum16(s, red, tx, ty) / nn : lane_sum16(s, red, tx, ty);
-  double q = 0.0;
-  if (c < C) {
-    for (int b = b0 + ty; b < b1; b += FIN_L) {
-      const long long o = ((long long)g * nblk + b) * C + c;
-      const double d = (double)pmean[o] - mu;
-      q += (double)pm2[o] + pcnt[(long long)g * nblk + b] * d * d;
-    }
-  }
-  const double mm = lane_sum16(q, red, tx, ty);
+  const double mm = merge_m2(g, c, C, nblk, b0, b1, mu, pmean, pm2, pcnt, red, tx, ty);
   if (ty != 0 || c >= C) return;
   double* o = seg + (((long long)g * S + sg) * C + c) * 3;
   o[0] = nn;
@@ -323,20 +319,6 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const typename S::T* __re
   }
 }
 
-// ReLU mask of the BN output: from the stored output when there is one (residual blocks),
-// else recomputed from y (lazily-applied BN: out = relu(y*scale + shift) was never stored).
-template <class S>
-__device__ __forceinline__ floatx4 relu_mask(floatx4 dz, const typename S::T* out, long long o,
-                                             floatx4 yv, const float* scale,
-                                             const float* shift, int gc) {
-  floatx4 pre;
-  if (out) pre = S::ld4(out + o);
-  else pre = yv * *(const floatx4*)(scale + gc) + *(const floatx4*)(shift + gc);
-#pragma unroll
-  for (int e = 0; e < 4; ++e) dz[e] = pre[e] > 0.f ? dz[e] : 0.f;
-  return dz;
-}
-
 // Backward stage 1: per (g, block) partial sums of dz and dz*xhat per channel,
 // dz = dout * (relu ? out > 0 : 1), xhat = (y - mean) * invstd.
 template <class S>
@@ -348,12 +330,13 @@ __global__ __launch_bounds__(256) void bn_bwd_partial(const typename S::T* __res
                                                       const float* __restrict__ invstd,
                                                       const float* __restrict__ scale,
                                                       const float* __restrict__ shift,
-                                                      long long M, int C, int rpb, RowMap rm,
+                                                      long long M, int C, int rpb,
                                                       float* __restrict__ p1,
                                                       float* __restrict__ p2,
                                                       const unsigned char* __restrict__ mask) {
   // one 8-channel group per thread (C % 8 == 0, C <= 2048): tpr threads span a row, rp rows
-  // are walked in parallel
+  // are walked in parallel (RowSlab's arithmetic, spelt out: through the struct the compiler
+  // schedules this kernel's row loop differently)
   const int tpr = C / 8, rp = 256 / tpr;
   const int g = blockIdx.y, blk = blockIdx.x, nblk = gridDim.x;
   const int tid = threadIdx.x;
@@ -428,8 +411,26 @@ __global__ __launch_bounds__(256) void bn_bwd_partial(const typename S::T* __res
   }
 }
 
-// Backward stage 2: grid (C/64, G), 64 channels x 4 lanes: k1 = sum dz / M, k2 = sum
-// dz*xhat / M per (g,c) (double sums, fixed order).
+// (sum p1, sum p2) over partials [b0, b1) of channel c of group g, by the block's 16 lanes of
+// that channel as in merge_partials (double sums, fixed order).
+__device__ __forceinline__ double2 sum_partials(int g, int c, int C, int nblk, int b0, int b1,
+                                                const float* p1, const float* p2,
+                                                double (*red)[64], int tx, int ty) {
+  double a = 0.0, b = 0.0;
+  if (c < C) {
+    for (int k = b0 + ty; k < b1; k += FIN_L) {
+      const long long o = ((long long)g * nblk + k) * C + c;
+      a += p1[o];
+      b += p2[o];
+    }
+  }
+  a = lane_sum16(a, red, tx, ty);
+  b = lane_sum16(b, red, tx, ty);
+  return make_double2(a, b);
+}
+
+// Backward stage 2: grid (C/64, G), 64 channels x 16 lanes: k1 = sum dz / M, k2 = sum
+// dz*xhat / M per (g,c).
 __global__ __launch_bounds__(1024) void bn_bwd_final(int G, int nblk, int C, long long M,
                                                      const float* __restrict__ p1,
                                                      const float* __restrict__ p2,
@@ -438,19 +439,10 @@ __global__ __launch_bounds__(1024) void bn_bwd_final(int G, int nblk, int C, lon
   const int g = blockIdx.y, tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
   const int c = blockIdx.x * 64 + tx;
   __shared__ double red[FIN_L][64];
-  double a = 0.0, b = 0.0;
-  if (c < C) {
-    for (int k = ty; k < nblk; k += FIN_L) {
-      const long long o = ((long long)g * nblk + k) * C + c;
-      a += p1[o];
-      b += p2[o];
-    }
-  }
-  a = lane_sum16(a, red, tx, ty);
-  b = lane_sum16(b, red, tx, ty);
+  const double2 s = sum_partials(g, c, C, nblk, 0, nblk, p1, p2, red, tx, ty);
   if (ty != 0 || c >= C) return;
-  k1[g * C + c] = (float)(a / (double)M);
-  k2[g * C + c] = (float)(b / (double)M);
+  k1[g * C + c] = (float)(s.x / (double)M);
+  k2[g * C + c] = (float)(s.y / (double)M);
 }
 
 // Many partials per channel (the data-gradient epilogue's one per 128-row tile: thousands at the
@@ -471,20 +463,11 @@ __global__ __launch_bounds__(1024) void bn_bwd_seg(int nblk, int C, const float*
   const int c = blockIdx.x * 64 + tx;
   const int b0 = sg * SEGB, b1 = min(nblk, b0 + SEGB);
   __shared__ double red[FIN_L][64];
-  double a = 0.0, b = 0.0;
-  if (c < C) {
-    for (int k = b0 + ty; k < b1; k += FIN_L) {
-      const long long o = ((long long)g * nblk + k) * C + c;
-      a += p1[o];
-      b += p2[o];
-    }
-  }
-  a = lane_sum16(a, red, tx, ty);
-  b = lane_sum16(b, red, tx, ty);
+  const double2 s = sum_partials(g, c, C, nblk, b0, b1, p1, p2, red, tx, ty);
   if (ty != 0 || c >= C) return;
   double* o = seg + (((long long)g * S + sg) * C + c) * 2;
-  o[0] = a;
-  o[1] = b;
+  o[0] = s.x;
+  o[1] = s.y;
 }
 
 __global__ void bn_bwd_merge(int G, int S, int C, long long M, const double* __restrict__ seg,
@@ -522,56 +505,35 @@ __global__ void bn_bwd_param_kernel(int G, int C, long long M, const float* __re
   if (dbeta) dbeta[c] += (float)(tb * (double)M);
 }
 
-// dy = gamma*invstd * (dz - k1 - xhat*k2); dres = dz (optional).  8 channels per iteration.
-template <class S>
-__global__ __launch_bounds__(256) void bn_bwd_apply(const typename S::T* __restrict__ y,
-                                                    const typename S::T* __restrict__ out,
-                                                    const typename S::T* __restrict__ dout,
-                                                    int relu,
-                                                    const float* __restrict__ mean,
-                                                    const float* __restrict__ invstd,
-                                                    const float* __restrict__ scale,
-                                                    const float* __restrict__ shift,
-                                                    const float* __restrict__ k1,
-                                                    const float* __restrict__ k2,
-                                                    typename S::T* __restrict__ dy,
-                                                    typename S::T* __restrict__ dres, long long M,
-                                                    int C) {
-  const int c8n = C / 8;
-  const long long per_g = M * c8n;
-  const int g = blockIdx.y;
-  const long long go = (long long)g * M * C;
-  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < per_g; i += (long long)gridDim.x * 256) {
-    const int c = 8 * (int)(i % c8n);
-    const long long o = go + 8 * i;
-    floatx8 dz = S::ld8(dout + o);
-    const floatx8 yv = S::ld8(y + o);
-    const int gc = g * C + c;
-    if (relu) {
-      const floatx8 pre = out ? S::ld8(out + o) : yv * ldf8(scale + gc) + ldf8(shift + gc);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) dz[e] = pre[e] > 0.f ? dz[e] : 0.f;
-    }
-    const floatx8 xh = (yv - ldf8(mean + gc)) * ldf8(invstd + gc);
-    S::st8(dy + o, ldf8(scale + gc) * (dz - ldf8(k1 + gc) - xh * ldf8(k2 + gc)));
-    if (dres) S::st8(dres + o, dz);
+// Row-walk forms of the two elementwise passes (RowSlab; the forward apply's default, the
+// backward apply's only form): a thread keeps its 8 channels' per-group parameters in registers
+// for the whole slab and its offsets need no 64-bit modulo — the grid-stride form
+// (bn_apply_kernel) reloads scale/shift (L1 hits, but issue slots) and divides per element
+// group, which is what held the 16-bit passes (48 B of HBM traffic per iteration) well below the
+// fp32 ones' bandwidth.  C <= 2048.
+// A thread's place in a row-walk block (C % 8 == 0, C <= 2048): C/8 threads of 8 channels span
+// a row and rp = 256/(C/8) rows are walked in parallel; the constructor gives the thread's row
+// t_r (t_r >= rp: no row, the thread leaves) and channel group t_c.  slab() then places the
+// block: blockIdx.x takes rows [r0, r1) of group blockIdx.y, row r's 8 elements are at
+// base + r * C and the thread's per-(group, channel) parameters at gc.
+struct RowSlab {
+  int rp, t_c, t_r, gc;
+  long long r0, r1, base;
+  __device__ __forceinline__ RowSlab(int C) {
+    const int tpr = C / 8, tid = threadIdx.x;
+    rp = 256 / tpr;
+    t_c = tid % tpr;
+    t_r = tid / tpr;
   }
-}
+  __device__ __forceinline__ void slab(long long M, int C, int rpb) {
+    const int g = blockIdx.y, c0 = 8 * t_c;
+    r0 = (long long)blockIdx.x * rpb;
+    r1 = min(M, r0 + rpb);
+    gc = g * C + c0;
+    base = (long long)g * M * C + c0;
+  }
+};
 
-// bn_bwd_partial geometry: C/8 threads span a row, so a 256-thread block walks 256/(C/8)
-// rows at once; at most 32 rows per thread keeps G*nblk in the hundreds for the deep,
-// narrow-M layers (layer4: M = B*49 rows of 2048 channels) that one-block-per-256-rows left at
-// ~13 blocks per group, at the cost of <= 1/32 extra partial traffic per element (32 vs 16 vs
-// 8 rows per thread with the ReLU masks: 234.5-235.5 vs 231.8-232.5 vs 230.9-232.0 fp32
-// triplets/s, 574-575 vs 562-565 vs 554 bf16 on one box, tools/gpubatch_rpt2.sh).
-static int ew_grid(long long n4);
-
-// Row-walk forms of the two elementwise passes (the default): C/8 threads span a row, 256/(C/8)
-// rows are walked in parallel and each block takes rpb consecutive rows, so a thread keeps its
-// 8 channels' per-group parameters in registers for the whole slab and its offsets need no
-// 64-bit modulo — the grid-stride forms above reload scale/shift (L1 hits, but issue slots) and
-// divide per element group, which is what held the 16-bit passes (48 B of HBM traffic per
-// iteration) well below the fp32 ones' bandwidth.  C <= 2048.
 template <class S>
 __global__ __launch_bounds__(256) void bn_apply_rows(const typename S::T* __restrict__ y,
                                                      const float* __restrict__ scale,
@@ -582,34 +544,29 @@ __global__ __launch_bounds__(256) void bn_apply_rows(const typename S::T* __rest
                                                      int relu, typename S::T* __restrict__ out,
                                                      long long M, int C, int rpb,
                                                      unsigned char* __restrict__ mask) {
-  const int tpr = C / 8, rp = 256 / tpr;
-  const int tid = threadIdx.x, t_c = tid % tpr, t_r = tid / tpr;
-  if (t_r >= rp) return;
-  const int g = blockIdx.y;
-  const long long r0 = (long long)blockIdx.x * rpb;
-  const long long r1 = min(M, r0 + rpb);
-  const int c0 = 8 * t_c, gc = g * C + c0;
-  const floatx8 sc = ldf8(scale + gc), sh = ldf8(shift + gc);
+  RowSlab t(C);
+  if (t.t_r >= t.rp) return;
+  t.slab(M, C, rpb);
+  const floatx8 sc = ldf8(scale + t.gc), sh = ldf8(shift + t.gc);
   floatx8 rsc, rsh;
-  if (res_scale) { rsc = ldf8(res_scale + gc); rsh = ldf8(res_shift + gc); }
-  const long long base = (long long)g * M * C + c0;
+  if (res_scale) { rsc = ldf8(res_scale + t.gc); rsh = ldf8(res_shift + t.gc); }
   // RU rows per step, every row's loads (y, the residual) issued before the first is used, the
   // residual's form chosen outside the loop (bn_bwd_apply_rows' reasoning)
   constexpr int RU = 2;
   auto rows = [&](auto rk) {
     constexpr int RES = decltype(rk)::value;  // 0 none, 1 res, 2 res * res_scale + res_shift
-    for (long long r = r0 + t_r; r < r1; r += RU * rp) {
+    for (long long r = t.r0 + t.t_r; r < t.r1; r += RU * t.rp) {
       typename S::R8 yr[RU], rr_[RU];
 #pragma unroll
       for (int u = 0; u < RU; ++u) {
-        const long long rr = r + (long long)u * rp;
-        const long long o = base + (rr < r1 ? rr : r) * C;   // past r1: row r again, not stored
+        const long long rr = r + (long long)u * t.rp;
+        const long long o = t.base + (rr < t.r1 ? rr : r) * C;   // past r1: row r again, not stored
         yr[u] = S::raw8(y + o);
         if constexpr (RES != 0) rr_[u] = S::raw8(res + o);
       }
 #pragma unroll
       for (int u = 0; u < RU; ++u) {
-        const long long rr = r + (long long)u * rp;
+        const long long rr = r + (long long)u * t.rp;
         floatx8 v = S::cvt8(yr[u]) * sc + sh;
         if constexpr (RES != 0) {
           floatx8 rv = S::cvt8(rr_[u]);
@@ -620,8 +577,8 @@ __global__ __launch_bounds__(256) void bn_apply_rows(const typename S::T* __rest
 #pragma unroll
           for (int e = 0; e < 8; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
         }
-        if (rr >= r1) continue;
-        const long long o = base + rr * C;
+        if (rr >= t.r1) continue;
+        const long long o = t.base + rr * C;
         S::st8(out + o, v);
         if (mask) {  // bit e = (stored out > 0): the value as rounded to the storage type
           alignas(16) typename S::T tmp[8];
@@ -655,31 +612,26 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_rows(const typename S::T* __
                                                          typename S::T* __restrict__ dres,
                                                          long long M, int C, int rpb,
                                                          const unsigned char* __restrict__ mask) {
-  const int tpr = C / 8, rp = 256 / tpr;
-  const int tid = threadIdx.x, t_c = tid % tpr, t_r = tid / tpr;
-  if (t_r >= rp) return;
-  const int g = blockIdx.y;
-  const long long r0 = (long long)blockIdx.x * rpb;
-  const long long r1 = min(M, r0 + rpb);
-  const int c0 = 8 * t_c, gc = g * C + c0;
-  const floatx8 sc = ldf8(scale + gc), mu = ldf8(mean + gc), is = ldf8(invstd + gc);
-  const floatx8 a1 = ldf8(k1 + gc), a2 = ldf8(k2 + gc);
+  RowSlab t(C);
+  if (t.t_r >= t.rp) return;
+  t.slab(M, C, rpb);
+  const floatx8 sc = ldf8(scale + t.gc), mu = ldf8(mean + t.gc), is = ldf8(invstd + t.gc);
+  const floatx8 a1 = ldf8(k1 + t.gc), a2 = ldf8(k2 + t.gc);
   floatx8 sh = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  if (relu && !out && !mask) sh = ldf8(shift + gc);
-  const long long base = (long long)g * M * C + c0;
+  if (relu && !out && !mask) sh = ldf8(shift + t.gc);
   // RU rows per step with every load (dz, y, the mask byte / out) issued before the first use
   // and the ReLU source chosen outside the loop: in one loop body with the branches inside,
   // each row waited for dz and y, then for its mask byte, then stored — three latencies a row
   constexpr int RU = 2;
   auto rows = [&](auto src) {
     constexpr int SRC = decltype(src)::value;  // 0 none, 1 mask bits, 2 out, 3 y*scale+shift
-    for (long long r = r0 + t_r; r < r1; r += RU * rp) {
+    for (long long r = t.r0 + t.t_r; r < t.r1; r += RU * t.rp) {
       typename S::R8 yr[RU], dr[RU], pr[RU];
       unsigned m[RU];
 #pragma unroll
       for (int u = 0; u < RU; ++u) {
-        const long long rr = r + (long long)u * rp;
-        const long long o = base + (rr < r1 ? rr : r) * C;   // past r1: row r again, not stored
+        const long long rr = r + (long long)u * t.rp;
+        const long long o = t.base + (rr < t.r1 ? rr : r) * C;   // past r1: row r again, not stored
         dr[u] = S::raw8(dout + o);
         yr[u] = S::raw8(y + o);
         if constexpr (SRC == 1) m[u] = mask[o >> 3];
@@ -687,7 +639,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_rows(const typename S::T* __
       }
 #pragma unroll
       for (int u = 0; u < RU; ++u) {
-        const long long rr = r + (long long)u * rp;
+        const long long rr = r + (long long)u * t.rp;
         const floatx8 yv = S::cvt8(yr[u]);
         floatx8 dz = S::cvt8(dr[u]);
         if constexpr (SRC == 1) {
@@ -698,8 +650,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_rows(const typename S::T* __
 #pragma unroll
           for (int e = 0; e < 8; ++e) dz[e] = p[e] > 0.f ? dz[e] : 0.f;
         }
-        if (rr < r1) {
-          const long long o = base + rr * C;
+        if (rr < t.r1) {
+          const long long o = t.base + rr * C;
           const floatx8 xh = (yv - mu) * is;
           S::st8(dy + o, sc * (dz - a1 - xh * a2));
           if (dres) S::st8(dres + o, dz);
@@ -713,34 +665,35 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_rows(const typename S::T* __
   else rows(std::integral_constant<int, 3>());
 }
 
-// Row-walk geometry: <= 2 rows per thread (measured 2 vs 4 vs 8 vs 16: inference 10.40-10.43k vs 10.32-10.35k vs 10.16-10.19k vs 10.12k
-// MC-samples/s on one box; training flat).
-static void rows_geometry(long long M, int C, int& nblk, int& rpb) {
-  constexpr int rpt = 2;
-  const int rp = 256 / (C / 8);
-  const long long r = (long long)rp * rpt;
-  rpb = (int)r;
-  nblk = (int)((M + r - 1) / r);
+// ---- launch geometry ----
+// bn_stats_partial: float4 per thread, up to 256 threads per row, the rest of the block's
+// threads on further rows.
+static inline RowMap row_map(int C) {
+  RowMap r;
+  const int c4 = C / 4;
+  r.tpr = c4 < 256 ? c4 : 256;
+  r.rp = 256 / r.tpr;
+  r.cpt = c4 / r.tpr;
+  return r;
 }
 
-static bool use_rows(int C) { return C % 8 == 0 && C <= 2048; }
-
-template <class S>
-static void launch_apply(const typename S::T* y, const float* scale, const float* shift,
-                         const typename S::T* res, const float* res_scale, const float* res_shift,
-                         int relu, typename S::T* out, int G, long long M, int C,
-                         hipStream_t stream, unsigned char* mask = nullptr) {
-  if (mask || use_rows(C)) {
-    int nblk, rpb;
-    rows_geometry(M, C, nblk, rpb);
-    hipLaunchKernelGGL(bn_apply_rows<S>, dim3(nblk, G), dim3(256), 0, stream, y, scale, shift,
-                       res, res_scale, res_shift, relu, out, M, C, rpb, mask);
-  } else {
-    hipLaunchKernelGGL(bn_apply_kernel<S>, dim3(ew_grid(M * C / 8), G), dim3(256), 0, stream, y,
-                       scale, shift, res, res_scale, res_shift, relu, out, M, C);
-  }
+// bn_stats_partial: ~256 rows per block, at most 1024 blocks per group.
+static void reduce_geometry(long long M, int C, int& nblk, int& rpb) {
+  const RowMap rm = row_map(C);
+  long long target = (M + 255) / 256;
+  if (target > 1024) target = 1024;
+  if (target < 1) target = 1;
+  rpb = (int)((M + target - 1) / target);
+  if (rpb < rm.rp) rpb = rm.rp;
+  nblk = (int)((M + rpb - 1) / rpb);
 }
 
+// bn_bwd_partial: C/8 threads span a row, so a 256-thread block walks 256/(C/8)
+// rows at once; at most 32 rows per thread keeps G*nblk in the hundreds for the deep,
+// narrow-M layers (layer4: M = B*49 rows of 2048 channels) that one-block-per-256-rows left at
+// ~13 blocks per group, at the cost of <= 1/32 extra partial traffic per element (32 vs 16 vs
+// 8 rows per thread with the ReLU masks: 234.5-235.5 vs 231.8-232.5 vs 230.9-232.0 fp32
+// triplets/s, 574-575 vs 562-565 vs 554 bf16 on one box, tools/gpubatch_rpt2.sh).
 static void bwd_geometry(long long M, int C, int& nblk, int& rpb) {
   constexpr int rpt = 32;  // rows per thread of the backward partial pass
   const int rp = 256 / (C / 8);
@@ -754,20 +707,41 @@ static void bwd_geometry(long long M, int C, int& nblk, int& rpb) {
   nblk = (int)((M + r - 1) / r);
 }
 
-static void reduce_geometry(long long M, int C, int& nblk, int& rpb) {
-  const RowMap rm = row_map(C);
-  long long target = (M + 255) / 256;  // ~256 rows per block
-  if (target > 1024) target = 1024;
-  if (target < 1) target = 1;
-  rpb = (int)((M + target - 1) / target);
-  if (rpb < rm.rp) rpb = rm.rp;
-  nblk = (int)((M + rpb - 1) / rpb);
+// bn_apply_rows / bn_bwd_apply_rows: <= 2 rows per thread (measured 2 vs 4 vs 8 vs 16: inference
+// 10.40-10.43k vs 10.32-10.35k vs 10.16-10.19k vs 10.12k MC-samples/s on one box; training
+// flat).
+static void rows_geometry(long long M, int C, int& nblk, int& rpb) {
+  constexpr int rpt = 2;
+  const int rp = 256 / (C / 8);
+  const long long r = (long long)rp * rpt;
+  rpb = (int)r;
+  nblk = (int)((M + r - 1) / r);
 }
 
-static int ew_grid(long long n4) {
-  long long b = (n4 + 255) / 256;
+// the channel counts the row-walk kernels take (RowSlab)
+static bool use_rows(int C) { return C % 8 == 0 && C <= 2048; }
+
+// bn_apply_kernel: grid-stride over n8 8-channel groups, at most 4096 blocks per group
+static int ew_grid(long long n8) {
+  long long b = (n8 + 255) / 256;
   if (b > 4096) b = 4096;
   return (int)(b < 1 ? 1 : b);
+}
+
+template <class S>
+static void launch_apply(const typename S::T* y, const float* scale, const float* shift,
+                         const typename S::T* res, const float* res_scale, const float* res_shift,
+                         int relu, typename S::T* out, int G, long long M, int C,
+                         hipStream_t stream, unsigned char* mask) {
+  if (mask || use_rows(C)) {
+    int nblk, rpb;
+    rows_geometry(M, C, nblk, rpb);
+    hipLaunchKernelGGL(bn_apply_rows<S>, dim3(nblk, G), dim3(256), 0, stream, y, scale, shift,
+                       res, res_scale, res_shift, relu, out, M, C, rpb, mask);
+  } else {
+    hipLaunchKernelGGL(bn_apply_kernel<S>, dim3(ew_grid(M * C / 8), G), dim3(256), 0, stream, y,
+                       scale, shift, res, res_scale, res_shift, relu, out, M, C);
+  }
 }
 
 // eval-mode BN (running statistics): per-group copies of scale/shift
@@ -837,7 +811,7 @@ MAUV_API int mauv_bn_fwd_train(const float* y, int G, long long M, int C, const 
     hipLaunchKernelGGL(bn_running_kernel, dim3((C + 255) / 256), dim3(256), 0, stream, G, C, uvar,
                        run_mean, run_var, momentum);
   if (out) {
-    launch_apply<SF32>(y, scale, shift, res, nullptr, nullptr, relu, out, G, M, C, stream);
+    launch_apply<SF32>(y, scale, shift, res, nullptr, nullptr, relu, out, G, M, C, stream, nullptr);
   }
   return check_launch("bn_fwd_train");
 }
@@ -857,14 +831,20 @@ MAUV_API int mauv_bn_stats_finalize(int G, int nblk, int C, const float* pmean, 
   return check_launch("bn_stats_finalize");
 }
 
-// out = [relu](y * scale + shift (+ res')) with precomputed per-group scale/shift;
-// res' = res * res_scale + res_shift when res_scale is given (pending BN on the residual).
-MAUV_API int mauv_bn_apply(const float* y, const float* scale, const float* shift,
-                           const float* res, const float* res_scale, const float* res_shift,
-                           int relu, float* out, int G, long long M, int C, hipStream_t stream) {
-  if (C % 8 != 0) { set_error("bn_apply: C % 8 != 0"); return kErrArg; }
-  launch_apply<SF32>(y, scale, shift, res, res_scale, res_shift, relu, out, G, M, C, stream);
-  return check_launch("bn_apply");
+// The forward apply of every entry: dtype -1 = fp32, 0 = bf16, 1 = f16 (y/res/out in that
+// type); mask (nullable): also write the ReLU mask bits of out.
+static int bn_apply_any(const char* what, int dtype, const void* y, const float* scale,
+                        const float* shift, const void* res, const float* res_scale,
+                        const float* res_shift, int relu, void* out, int G, long long M, int C,
+                        hipStream_t stream, unsigned char* mask) {
+#define L(D) launch_apply<S16<D>>((const u16*)y, scale, shift, (const u16*)res, res_scale,  \
+                                  res_shift, relu, (u16*)out, G, M, C, stream, mask);
+  if (dtype < 0)
+    launch_apply<SF32>((const float*)y, scale, shift, (const float*)res, res_scale, res_shift,
+                       relu, (float*)out, G, M, C, stream, mask);
+  else MAUV_DT_DISPATCH(dtype, what, L)
+#undef L
+  return check_launch(what);
 }
 
 template <class S>
@@ -874,12 +854,11 @@ static int bn_bwd_impl(const typename S::T* y, const typename S::T* out,
                        long long M, int C, float* workspace, typename S::T* dy,
                        typename S::T* dres, float* dgamma, float* dbeta, const float* pre_p1,
                        const float* pre_p2, int pre_nblk, hipStream_t stream,
-                       const unsigned char* mask = nullptr) {
-  if (C % 8 != 0 || C > 2048) { set_error("bn_bwd: unsupported C (C % 8 != 0 or > 2048)"); return kErrArg; }
+                       const unsigned char* mask) {
+  if (!use_rows(C)) { set_error("bn_bwd: unsupported C (C % 8 != 0 or > 2048)"); return kErrArg; }
   if (relu && !out && !shift && !mask) { set_error("bn_bwd: relu mask needs out or scale/shift"); return kErrArg; }
   int nblk, rpb;
   bwd_geometry(M, C, nblk, rpb);
-  const RowMap rm = row_map(C);
   float* p1 = workspace;
   float* p2 = p1 + (long long)G * nblk * C;
   float* k1 = p2 + (long long)G * nblk * C;
@@ -891,7 +870,7 @@ static int bn_bwd_impl(const typename S::T* y, const typename S::T* out,
     q1 = pre_p1; q2 = pre_p2; qn = pre_nblk;
   } else {
     hipLaunchKernelGGL(bn_bwd_partial<S>, dim3(nblk, G), dim3(256), 0, stream, y, out, dout,
-                       relu, mean, invstd, scale, shift, M, C, rpb, rm, p1, p2, mask);
+                       relu, mean, invstd, scale, shift, M, C, rpb, p1, p2, mask);
   }
   const int nseg = qn > kSegAbove ? bwd_segs(qn) : 1;
   if (nseg > 1) {
@@ -908,29 +887,47 @@ static int bn_bwd_impl(const typename S::T* y, const typename S::T* out,
                          M, k1, k2, dgamma, dbeta);
   }
   if (!dy && !dres) return check_launch("bn_bwd");   // partial sums / parameter grads only
-  if (mask || use_rows(C)) {
-    int anblk, arpb;
-    rows_geometry(M, C, anblk, arpb);
-    hipLaunchKernelGGL(bn_bwd_apply_rows<S>, dim3(anblk, G), dim3(256), 0, stream, y, out, dout,
-                       relu, mean, invstd, scale, shift, k1, k2, dy, dres, M, C, arpb, mask);
-  } else {
-    hipLaunchKernelGGL(bn_bwd_apply<S>, dim3(ew_grid(M * C / 8), G), dim3(256), 0, stream, y, out,
-                       dout, relu, mean, invstd, scale, shift, k1, k2, dy, dres, M, C);
-  }
+  int anblk, arpb;
+  rows_geometry(M, C, anblk, arpb);
+  hipLaunchKernelGGL(bn_bwd_apply_rows<S>, dim3(anblk, G), dim3(256), 0, stream, y, out, dout,
+                     relu, mean, invstd, scale, shift, k1, k2, dy, dres, M, C, arpb, mask);
   return check_launch("bn_bwd");
 }
 
-// Training-mode BN backward (+ReLU mask from `out`, + residual split):
-//   dy = gamma*invstd*(dz - mean(dz) - xhat*mean(dz*xhat)),  dres = dz (nullable),
-//   dgamma += sum dz*xhat, dbeta += sum dz (over all groups; nullable).
-MAUV_API int mauv_bn_bwd(const float* y, const float* out, const float* dout, int relu,
-                         const float* mean, const float* invstd, const float* scale,
-                         const float* shift, int G, long long M, int C, float* workspace,
-                         float* dy, float* dres, float* dgamma, float* dbeta,
-                         const float* pre_p1, const float* pre_p2, int pre_nblk,
-                         hipStream_t stream) {
-  return bn_bwd_impl<SF32>(y, out, dout, relu, mean, invstd, scale, shift, G, M, C, workspace,
-                           dy, dres, dgamma, dbeta, pre_p1, pre_p2, pre_nblk, stream);
+// The backward of every entry (dtype as bn_apply_any): partial sums (or pre_p1/pre_p2 of
+// pre_nblk blocks in their place), finalize, parameter gradients, then the apply pass.
+static int bn_bwd_any(const char* what, int dtype, const void* y, const void* out,
+                      const void* dout, int relu, const float* mean, const float* invstd,
+                      const float* scale, const float* shift, int G, long long M, int C,
+                      float* workspace, void* dy, void* dres, float* dgamma, float* dbeta,
+                      const float* pre_p1, const float* pre_p2, int pre_nblk,
+                      hipStream_t stream, const unsigned char* mask) {
+  if (dtype < 0)
+    return bn_bwd_impl<SF32>((const float*)y, (const float*)out, (const float*)dout, relu, mean,
+                             invstd, scale, shift, G, M, C, workspace, (float*)dy, (float*)dres,
+                             dgamma, dbeta, pre_p1, pre_p2, pre_nblk, stream, mask);
+#define L(D) return bn_bwd_impl<S16<D>>((const u16*)y, (const u16*)out, (const u16*)dout, relu, mean, \
+                                        invstd, scale, shift, G, M, C, workspace, (u16*)dy,       \
+                                        (u16*)dres, dgamma, dbeta, pre_p1, pre_p2, pre_nblk,      \
+                                        stream, mask);
+  MAUV_DT_DISPATCH(dtype, what, L)
+#undef L
+}
+
+// the 16-bit entries take no fp32 code
+static int no_f32(const char* what) {
+  set_error(std::string(what) + ": dtype must be 0 (bf16) or 1 (f16)");
+  return kErrArg;
+}
+
+// out = [relu](y * scale + shift (+ res')) with precomputed per-group scale/shift;
+// res' = res * res_scale + res_shift when res_scale is given (pending BN on the residual).
+MAUV_API int mauv_bn_apply(const float* y, const float* scale, const float* shift,
+                           const float* res, const float* res_scale, const float* res_shift,
+                           int relu, float* out, int G, long long M, int C, hipStream_t stream) {
+  if (C % 8 != 0) { set_error("bn_apply: C % 8 != 0"); return kErrArg; }
+  return bn_apply_any("bn_apply", -1, y, scale, shift, res, res_scale, res_shift, relu, out, G,
+                      M, C, stream, nullptr);
 }
 
 // 16-bit activations (dtype 0 = bf16, 1 = f16): y/out/dout/dy/dres are 16-bit, statistics,
@@ -940,23 +937,9 @@ MAUV_API int mauv_bn_apply_h16(int dtype, const void* y, const float* scale, con
                                int relu, void* out, int G, long long M, int C,
                                hipStream_t stream) {
   if (C % 8 != 0) { set_error("bn_apply_h16: C % 8 != 0"); return kErrArg; }
-#define L(D) launch_apply<S16<D>>((const u16*)y, scale, shift, (const u16*)res, res_scale,  \
-                                  res_shift, relu, (u16*)out, G, M, C, stream);
-  MAUV_DT_DISPATCH(dtype, "bn_apply_h16", L)
-#undef L
-  return check_launch("bn_apply_h16");
-}
-
-MAUV_API int mauv_bn_bwd_h16(int dtype, const void* y, const void* out, const void* dout,
-                             int relu, const float* mean, const float* invstd, const float* scale,
-                             const float* shift, int G, long long M, int C, float* workspace,
-                             void* dy, void* dres, float* dgamma, float* dbeta,
-                             hipStream_t stream) {
-#define L(D) return bn_bwd_impl<S16<D>>((const u16*)y, (const u16*)out, (const u16*)dout, relu, mean, \
-                                        invstd, scale, shift, G, M, C, workspace, (u16*)dy,       \
-                                        (u16*)dres, dgamma, dbeta, nullptr, nullptr, 0, stream);
-  MAUV_DT_DISPATCH(dtype, "bn_bwd_h16", L)
-#undef L
+  if (dtype < 0) return no_f32("bn_apply_h16");
+  return bn_apply_any("bn_apply_h16", dtype, y, scale, shift, res, res_scale, res_shift, relu,
+                      out, G, M, C, stream, nullptr);
 }
 
 // Block-output BN apply that also writes the ReLU mask bits of the stored output (training):
@@ -967,36 +950,14 @@ MAUV_API int mauv_bn_apply_mask(int dtype, const void* y, const float* scale, co
                                 void* out, unsigned char* mask, int G, long long M, int C,
                                 hipStream_t stream) {
   if (C % 8 != 0 || C > 2048 || !mask) { set_error("bn_apply_mask: C % 8 != 0, C > 2048 or no mask"); return kErrArg; }
-  if (dtype < 0) {
-    launch_apply<SF32>((const float*)y, scale, shift, (const float*)res, res_scale, res_shift, 1,
-                       (float*)out, G, M, C, stream, mask);
-    return check_launch("bn_apply_mask");
-  }
-#define L(D) launch_apply<S16<D>>((const u16*)y, scale, shift, (const u16*)res, res_scale,  \
-                                  res_shift, 1, (u16*)out, G, M, C, stream, mask);
-  MAUV_DT_DISPATCH(dtype, "bn_apply_mask", L)
-#undef L
-  return check_launch("bn_apply_mask");
+  return bn_apply_any("bn_apply_mask", dtype, y, scale, shift, res, res_scale, res_shift, 1, out,
+                      G, M, C, stream, mask);
 }
 
-// BN + ReLU backward with the ReLU mask from mauv_bn_apply_mask (instead of the output).
-MAUV_API int mauv_bn_bwd_mask(int dtype, const void* y, const unsigned char* mask,
-                              const void* dout, const float* mean, const float* invstd,
-                              const float* scale, int G, long long M, int C, float* workspace,
-                              void* dy, void* dres, float* dgamma, float* dbeta,
-                              hipStream_t stream) {
-  if (!mask) { set_error("bn_bwd_mask: no mask"); return kErrArg; }
-  if (dtype < 0)
-    return bn_bwd_impl<SF32>((const float*)y, nullptr, (const float*)dout, 1, mean, invstd, scale,
-                             nullptr, G, M, C, workspace, (float*)dy, (float*)dres, dgamma, dbeta,
-                             nullptr, nullptr, 0, stream, mask);
-#define L(D) return bn_bwd_impl<S16<D>>((const u16*)y, nullptr, (const u16*)dout, 1, mean, invstd,  \
-                                        scale, nullptr, G, M, C, workspace, (u16*)dy, (u16*)dres, \
-                                        dgamma, dbeta, nullptr, nullptr, 0, stream, mask);
-  MAUV_DT_DISPATCH(dtype, "bn_bwd_mask", L)
-#undef L
-}
-
+// Training-mode BN backward, the definition of every backward entry (include/mauv.h):
+//   dz = dout where the ReLU passed (`mask` bits, else relu ? (out, or y*scale+shift) > 0 : all),
+//   dy = gamma*invstd*(dz - mean(dz) - xhat*mean(dz*xhat)),  dres = dz (nullable),
+//   dgamma += sum dz*xhat, dbeta += sum dz (over all groups; nullable).
 MAUV_API int mauv_bn_bwd_ex(int dtype, const void* y, const void* out, const unsigned char* mask,
                             const void* dout, int relu, const float* mean, const float* invstd,
                             const float* scale, const float* shift, int G, long long M, int C,
@@ -1005,14 +966,39 @@ MAUV_API int mauv_bn_bwd_ex(int dtype, const void* y, const void* out, const uns
                             hipStream_t stream) {
   if (pre_p1 && (!pre_p2 || pre_nblk <= 0)) { set_error("bn_bwd_ex: pre_p1 needs pre_p2 and pre_nblk > 0"); return kErrArg; }
   if (mask) relu = 1, out = nullptr;
-  if (dtype < 0)
-    return bn_bwd_impl<SF32>((const float*)y, (const float*)out, (const float*)dout, relu, mean,
-                             invstd, scale, shift, G, M, C, workspace, (float*)dy, (float*)dres,
-                             dgamma, dbeta, pre_p1, pre_p2, pre_nblk, stream, mask);
-#define L(D) return bn_bwd_impl<S16<D>>((const u16*)y, (const u16*)out, (const u16*)dout, relu, mean, \
-                                        invstd, scale, shift, G, M, C, workspace, (u16*)dy,       \
-                                        (u16*)dres, dgamma, dbeta, pre_p1, pre_p2, pre_nblk,      \
-                                        stream, mask);
-  MAUV_DT_DISPATCH(dtype, "bn_bwd_ex", L)
-#undef L
+  return bn_bwd_any("bn_bwd_ex", dtype, y, out, dout, relu, mean, invstd, scale, shift, G, M, C,
+                    workspace, dy, dres, dgamma, dbeta, pre_p1, pre_p2, pre_nblk, stream, mask);
+}
+
+// mauv_bn_bwd_ex with dtype -1 (fp32) and no mask bits
+MAUV_API int mauv_bn_bwd(const float* y, const float* out, const float* dout, int relu,
+                         const float* mean, const float* invstd, const float* scale,
+                         const float* shift, int G, long long M, int C, float* workspace,
+                         float* dy, float* dres, float* dgamma, float* dbeta,
+                         const float* pre_p1, const float* pre_p2, int pre_nblk,
+                         hipStream_t stream) {
+  return bn_bwd_any("bn_bwd", -1, y, out, dout, relu, mean, invstd, scale, shift, G, M, C,
+                    workspace, dy, dres, dgamma, dbeta, pre_p1, pre_p2, pre_nblk, stream, nullptr);
+}
+
+// mauv_bn_bwd_ex for the 16-bit types, no mask bits, no pre-computed partials
+MAUV_API int mauv_bn_bwd_h16(int dtype, const void* y, const void* out, const void* dout,
+                             int relu, const float* mean, const float* invstd, const float* scale,
+                             const float* shift, int G, long long M, int C, float* workspace,
+                             void* dy, void* dres, float* dgamma, float* dbeta,
+                             hipStream_t stream) {
+  if (dtype < 0) return no_f32("bn_bwd_h16");
+  return bn_bwd_any("bn_bwd_h16", dtype, y, out, dout, relu, mean, invstd, scale, shift, G, M, C,
+                    workspace, dy, dres, dgamma, dbeta, nullptr, nullptr, 0, stream, nullptr);
+}
+
+// mauv_bn_bwd_ex with the mask bits of mauv_bn_apply_mask: no out, shift or pre-computed partials
+MAUV_API int mauv_bn_bwd_mask(int dtype, const void* y, const unsigned char* mask,
+                              const void* dout, const float* mean, const float* invstd,
+                              const float* scale, int G, long long M, int C, float* workspace,
+                              void* dy, void* dres, float* dgamma, float* dbeta,
+                              hipStream_t stream) {
+  if (!mask) { set_error("bn_bwd_mask: no mask"); return kErrArg; }
+  return bn_bwd_any("bn_bwd_mask", dtype, y, nullptr, dout, 1, mean, invstd, scale, nullptr, G, M,
+                    C, workspace, dy, dres, dgamma, dbeta, nullptr, nullptr, 0, stream, mask);
 }

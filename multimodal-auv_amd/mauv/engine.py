@@ -668,17 +668,10 @@ class TrunkRunner(_Runner):
         dg = bn.weight.grad if bn.weight.requires_grad else None
         db = bn.bias.grad if bn.bias.requires_grad else None
         s = rec.stats
-        if pre is not None:
-            ops.bn_bwd_ex(rec.y, None, rec.mask, dout, rec.relu, s[0], s[1], s[2], s[3], G, M, C,
-                          ws, dy, dres, dg, db, pre=(pre["p1"], pre["p2"], pre["nblk"]))
-        elif mask is not None:
-            ops.bn_bwd_ex(rec.y, None, mask, dout, 1, s[0], s[1], s[2], s[3], G, M, C, ws, dy,
-                          dres, dg, db)
-        elif rec.mask is not None:
-            ops.bn_bwd_mask(rec.y, rec.mask, dout, s[0], s[1], s[2], G, M, C, ws, dy, dres, dg, db)
-        else:
-            ops.bn_bwd(rec.y, rec.out, dout, rec.relu, s[0], s[1], s[2], G, M, C, ws, dy, dres,
-                       dg, db, shift=s[3])
+        ops.bn_bwd_ex(rec.y, rec.out, mask if mask is not None else rec.mask, dout,
+                      1 if mask is not None else rec.relu, s[0], s[1], s[2], s[3], G, M, C, ws,
+                      dy, dres, dg, db,
+                      pre=None if pre is None else (pre["p1"], pre["p2"], pre["nblk"]))
         return dy, dres
 
     # ---- schedule ----

@@ -741,6 +741,53 @@ def test_bn_relu_mask_path_matches_output_path(dt, C, M, res_bn):
 
 @pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16, torch.float16],
                          ids=["fp32", "bf16", "f16"])
+@pytest.mark.parametrize("source", ["none", "lazy", "out", "mask"])
+@pytest.mark.parametrize("G,M,C", [
+    (3, 37, 24),     # 3 threads a row, 85 rows in parallel, one idle thread, one ragged slab
+    (2, 300, 256),   # 8 rows in parallel: 19 apply slabs (ragged last), 2 backward-partial blocks
+    (2, 37, 2048),   # 1 row in parallel, odd row count against 2 and 4 rows a step
+])
+def test_bn_entries_agree(dt, source, G, M, C):
+    """The older exported entries are bn_bwd_ex / one apply with arguments fixed: bn_bwd (ReLU
+    source none, lazy y*scale+shift, out) and bn_bwd_mask (mask bits) == bn_bwd_ex with the same
+    source on dy, dres, dgamma, dbeta, and bn_apply_mask's out == bn_apply(relu), bit for bit.
+    dy / dres / out / the workspace start as NaN, so an unwritten element fails; dgamma and
+    dbeta are accumulated into, so they start at 0."""
+    from mauv import ops
+    torch.manual_seed(29)
+    y = (torch.randn(G, M, C, device=dev) * 2).to(dt)
+    r = torch.randn(G, M, C, device=dev).to(dt)
+    s, h = torch.randn(G, C, device=dev), torch.randn(G, C, device=dev)
+    s[:, :8] = 0.0          # outputs exactly 0 -> masked
+    out_ref = torch.full_like(y, float("nan"))
+    ops.bn_apply(y, s, h, r, True, out_ref, G, M, C)
+    out = torch.full_like(y, float("nan"))
+    mask = torch.empty(G * M * C // 8, dtype=torch.uint8, device=dev)
+    ops.bn_apply_mask(y, s, h, r, out, mask, G, M, C)
+    assert torch.equal(out, out_ref)
+    mean, invstd = torch.randn(G, C, device=dev), torch.rand(G, C, device=dev) + 0.5
+    dout = torch.randn(G, M, C, device=dev).to(dt)
+    o = out_ref if source == "out" else None
+    res = []
+    for ex in (False, True):
+        ws = torch.full((ops.bn_workspace_floats(G, M, C),), float("nan"), device=dev)
+        dy, dres = torch.full_like(y, float("nan")), torch.full_like(y, float("nan"))
+        dg, db = torch.zeros(C, device=dev), torch.zeros(C, device=dev)
+        if ex:
+            ops.bn_bwd_ex(y, o, mask if source == "mask" else None, dout, source != "none", mean,
+                          invstd, s, h, G, M, C, ws, dy, dres, dg, db)
+        elif source == "mask":
+            ops.bn_bwd_mask(y, mask, dout, mean, invstd, s, G, M, C, ws, dy, dres, dg, db)
+        else:
+            ops.bn_bwd(y, o, dout, source != "none", mean, invstd, s, G, M, C, ws, dy, dres, dg,
+                       db, shift=h)
+        res.append((dy, dres, dg, db))
+    for a, b in zip(*res):
+        assert torch.equal(a, b)
+
+
+@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16, torch.float16],
+                         ids=["fp32", "bf16", "f16"])
 @pytest.mark.parametrize("G,Cout,Cin,R,cin_pad,explicit", [
     (5, 64, 64, 3, None, False), (5, 48, 1028, 1, None, False), (3, 7, 2048, 1, None, True),
     (4, 33, 20, 3, 24, True), (2, 16, 12, 7, None, False), (5, 8, 6, 3, None, False)])
