@@ -251,7 +251,8 @@ int mauv_kl_workspace_bytes(int n_entries);
 int mauv_kl_fwd(const MauvKlEntry* table, int n, double* workspace, float scale, float* out,
                 hipStream_t stream);
 /* dmu/drho += (coef_dev ? *coef_dev : 1) * scale * dKL/d(mu, rho) (coef_dev: device scalar,
- * the upstream gradient — no host sync). */
+ * the upstream gradient — no host sync).  An entry's dmu and drho may each be NULL (a frozen
+ * tensor has no gradient): that half of the entry is skipped, the other is still added. */
 int mauv_kl_bwd(const MauvKlEntry* table, int n, const float* coef_dev, float scale,
                 hipStream_t stream);
 /* test hook: raw Philox words [nq][4] and the derived normals [nq][4] */

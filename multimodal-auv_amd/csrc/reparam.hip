@@ -358,8 +358,9 @@ __global__ __launch_bounds__(256) void kl_bwd_kernel(const MauvKlEntry* __restri
   for (long long i = blockIdx.x * 256LL + threadIdx.x; i < t.numel; i += (long long)gridDim.x * 256) {
     const float r = t.rho[i];
     const float s = softplus(r);
-    t.dmu[i] += coef * (t.mu[i] - t.prior_mu) * inv_sp2;
-    t.drho[i] += coef * (-1.0f / s + s * inv_sp2) * sigmoidf_(r);
+    // a frozen tensor has no gradient: its pointer is null and that half is skipped
+    if (t.dmu) t.dmu[i] += coef * (t.mu[i] - t.prior_mu) * inv_sp2;
+    if (t.drho) t.drho[i] += coef * (-1.0f / s + s * inv_sp2) * sigmoidf_(r);
   }
 }
 
@@ -562,7 +563,8 @@ MAUV_API int mauv_kl_fwd(const MauvKlEntry* table, int n, double* workspace, flo
   return check_launch("kl_fwd");
 }
 
-// dmu/drho += (coef_dev ? *coef_dev : 1) * scale * dKL/d(mu,rho) for every table entry.
+// dmu/drho += (coef_dev ? *coef_dev : 1) * scale * dKL/d(mu,rho) for every table entry; a null
+// dmu or drho (frozen tensor) is skipped on its own.
 MAUV_API int mauv_kl_bwd(const MauvKlEntry* table, int n, const float* coef_dev, float scale,
                          hipStream_t stream) {
   if (n <= 0 || n > 65535) { set_error("kl_bwd: bad table size"); return kErrArg; }

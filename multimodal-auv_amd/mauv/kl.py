@@ -26,6 +26,11 @@ def _entries(modules):
     return out
 
 
+def _grad_ptr(t):
+    """The gradient a trainable tensor accumulates into; 0 for a frozen one (or no gradient)."""
+    return t.grad.data_ptr() if t.requires_grad and t.grad is not None else 0
+
+
 class KLTable:
     def __init__(self, modules):
         self.entries = _entries(modules)
@@ -41,9 +46,9 @@ class KLTable:
         for i, (mu, rho, pm, ps) in enumerate(self.entries):
             rows[i, 0] = mu.data_ptr()
             rows[i, 1] = rho.data_ptr()
-            if with_grads:
-                rows[i, 2] = mu.grad.data_ptr() if mu.grad is not None else 0
-                rows[i, 3] = rho.grad.data_ptr() if rho.grad is not None else 0
+            if with_grads:   # 0 (a frozen tensor): mauv_kl_bwd skips that half of the entry
+                rows[i, 2] = _grad_ptr(mu)
+                rows[i, 3] = _grad_ptr(rho)
             rows[i, 4] = mu.numel()
             rows[i, 5] = np.array([pm, ps], dtype=np.float32).view(np.int64)[0]
         return torch.from_numpy(rows).to(device)
@@ -61,12 +66,12 @@ class KLTable:
         return self._fwd
 
     def bwd_table(self, device):
-        key = self._ptr_key() + tuple((t.grad.data_ptr() if t.grad is not None else 0)
-                                      for e in self.entries for t in e[:2])
+        key = self._ptr_key() + tuple(_grad_ptr(t) for e in self.entries for t in e[:2])
         if self._bwd is None or self._bwd_key != key:
-            for mu, rho, _, _ in self.entries:
-                if mu.requires_grad and (mu.grad is None or rho.grad is None):
-                    raise RuntimeError("KL backward: gradient arena not attached")
+            for e in self.entries:
+                for t in e[:2]:   # each tensor on its own: mu may be frozen under a live rho
+                    if t.requires_grad and t.grad is None:
+                        raise RuntimeError("KL backward: gradient arena not attached")
             self._bwd = self._build(True, device)
             self._bwd_key = key
         return self._bwd

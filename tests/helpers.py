@@ -304,3 +304,69 @@ class NullWriter:
 
     def add_scalar(self, *a, **k):
         pass
+
+
+# ---- pooling kernels against torch in float64 (tests/test_kernels_gpu.py fp32, test_kernels16_gpu.py)
+# (N, H, W, C): one pixel, W != H throughout, odd and even extents, 1 to 8 channel chunks
+POOL_SHAPES = [(1, 1, 1, 8), (2, 2, 3, 8), (1, 4, 6, 16), (3, 7, 5, 24), (2, 9, 12, 64)]
+
+
+def check_maxpool(dt, N, H, W, C, close):
+    """maxpool_fwd + maxpool_bwd on N non-square NHWC images of storage type ``dt`` against
+    F.max_pool2d(return_indices=True) in float64 on the same rounded inputs: equal pooled values,
+    argmax bytes equal to torch's index as the tap r*3 + s of its window, dx against autograd
+    (``close``; bit-equal in fp32 wherever at most one window feeds the pixel).  A block of zeros
+    gives ties (first maximum in scan order) and one NaN input wins its windows, as in torch."""
+    import torch.nn.functional as F
+    from mauv import ops
+    torch.manual_seed(N * 1000 + H * 100 + W)
+    x = torch.randn(N, H, W, C).to(dt)
+    x[0, :3, :3, :] = 0.0
+    x[N - 1, H - 1, W // 2, 3] = float("nan")
+    Ho, Wo = ops.out_hw(H, 3, 2, 1), ops.out_hw(W, 3, 2, 1)
+    y = torch.empty(N, Ho, Wo, C, device="cuda", dtype=dt)
+    idx = torch.empty(N, Ho, Wo, C, dtype=torch.uint8, device="cuda")
+    ops.maxpool_fwd(x.cuda(), N, H, W, C, y, idx)
+    xr = x.double().permute(0, 3, 1, 2).requires_grad_(True)
+    yr, flat = F.max_pool2d(xr, 3, 2, 1, return_indices=True)
+    yk, yt = y.double().cpu(), yr.detach().permute(0, 2, 3, 1)
+    assert yt.isnan().any() and bool(((yk == yt) | (yk.isnan() & yt.isnan())).all())
+    oh = torch.arange(Ho).view(1, 1, Ho, 1)
+    ow = torch.arange(Wo).view(1, 1, 1, Wo)
+    tap = (flat // W - (2 * oh - 1)) * 3 + (flat % W - (2 * ow - 1))
+    assert bool(((tap >= 0) & (tap < 9)).all())
+    assert torch.equal(idx.cpu(), tap.permute(0, 2, 3, 1).to(torch.uint8))
+    dy = torch.randn(N, Ho, Wo, C).to(dt)
+    yr.backward(dy.double().permute(0, 3, 1, 2))
+    dx = torch.empty(N, H, W, C, device="cuda", dtype=dt)
+    ops.maxpool_bwd(dy.cuda(), idx, N, H, W, C, dx)
+    ref = xr.grad.permute(0, 2, 3, 1)
+    assert ref[N - 1, H - 1, W // 2, 3] != 0, "the NaN input takes its windows' gradient"
+    close(dx, ref)
+    if dt == torch.float32:
+        fed = torch.zeros(N, C, H * W).scatter_add_(2, flat.reshape(N, C, -1),
+                                                    torch.ones(N, C, Ho * Wo))
+        one = (fed <= 1).view(N, C, H, W).permute(0, 2, 3, 1)
+        assert torch.equal(dx.cpu().double()[one], ref[one])
+
+
+def check_avgpool(dt, N, HW, C):
+    """avgpool_fwd (fp32 means of ``dt`` storage) and avgpool_bwd against float64.  Bounds: a
+    sequential fp32 sum of HW terms errs at most HW 2^-24 sum|x|, so the mean at most
+    HW 2^-24 max|x|; dx = dy * fl(1/HW) takes two fp32 roundings (2^-23 |dx| to first order,
+    2^-22 asserted) and, for 16-bit storage, the rounding to it (half an ulp: 2^-8 |dx| bf16;
+    2^-11 |dx| f16, or 2^-25, half its subnormal spacing)."""
+    from mauv import ops
+    torch.manual_seed(HW * 10 + C)
+    x = torch.randn(N, HW, C).to(dt)
+    a = torch.empty(N, C, device="cuda")
+    ops.avgpool_fwd(x.cuda(), N, HW, C, a)
+    err = (a.double().cpu() - x.double().mean(1)).abs().max().item()
+    assert err <= (HW + 1) * 2.0 ** -24 * x.double().abs().max().item(), err
+    da = torch.randn(N, C)
+    dxa = torch.empty(N, HW, C, device="cuda", dtype=dt)
+    ops.avgpool_bwd(da.cuda(), N, HW, C, dxa)
+    ref = (da.double() / HW)[:, None, :].expand(N, HW, C)
+    rel = {torch.float32: 0.0, torch.bfloat16: 2.0 ** -8, torch.float16: 2.0 ** -11}[dt] + 2.0 ** -22
+    sub = 2.0 ** -25 if dt == torch.float16 else 0.0
+    assert bool(((dxa.double().cpu() - ref).abs() <= rel * ref.abs() + sub).all())

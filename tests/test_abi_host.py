@@ -191,6 +191,35 @@ def test_kl_table_packing():
     assert rows[0, 0] == lin.mu_weight.data_ptr() and rows[1, 1] == lin.rho_bias.data_ptr()
 
 
+def test_kl_table_frozen_tensor_has_null_gradient():
+    """A frozen mu gets 0 in the dmu column (mauv_kl_bwd skips a null pointer) beside the live
+    drho pointer of the same row, also when a stale .grad is still attached to it; every tensor
+    is checked by its own requires_grad: a trainable rho without a gradient raises."""
+    from mauv.kl import KLTable
+    from mauv.layers import LinearReparameterization
+    lin = LinearReparameterization(4, 3)
+    for p in lin.parameters():
+        p.grad = torch.zeros_like(p)
+    tab = KLTable([lin])
+    rows = tab._build(True, "cpu").numpy()
+    assert rows[0, 2] == lin.mu_weight.grad.data_ptr() and rows[1, 3] == lin.rho_bias.grad.data_ptr()
+    lin.mu_weight.requires_grad_(False)
+    for stale in (True, False):
+        if not stale:
+            lin.mu_weight.grad = None
+        rows = tab._build(True, "cpu").numpy()
+        assert rows[0, 2] == 0
+        assert rows[0, 3] == lin.rho_weight.grad.data_ptr() != 0
+        assert rows[1, 2] == lin.mu_bias.grad.data_ptr() and rows[1, 3] == lin.rho_bias.grad.data_ptr()
+        assert np.array_equal(tab.bwd_table("cpu").numpy(), rows)
+    lin.rho_weight.grad = None       # trainable rho under a frozen mu: still an error
+    with pytest.raises(RuntimeError, match="arena not attached"):
+        tab.bwd_table("cpu")
+    lin.rho_weight.requires_grad_(False)
+    rows = tab.bwd_table("cpu").numpy()
+    assert rows[0, 2] == 0 and rows[0, 3] == 0 and rows[1, 2] != 0 and rows[1, 3] != 0
+
+
 def test_engine_layer_ids_and_sample_counter():
     from mauv.models import define_models, DEFAULT_PRIOR
     from mauv.engine import root_state

@@ -266,6 +266,15 @@ def test_maxpool16_bwd_shapes(dt, N, H, C):
 
 
 @pytest.mark.parametrize("dt", DTYPES, ids=["bf16", "f16"])
+@pytest.mark.parametrize("shape", list(range(5)))
+def test_maxpool16_nonsquare_argmax_ties_nan(dt, shape):
+    """16-bit max-pool on H != W images: pooled values, argmax bytes and dx against torch
+    (tests.helpers.check_maxpool)."""
+    from tests.helpers import POOL_SHAPES, check_maxpool
+    check_maxpool(dt, *POOL_SHAPES[shape], lambda a, b: close(a, b, 2 * ULP[dt]))
+
+
+@pytest.mark.parametrize("dt", DTYPES, ids=["bf16", "f16"])
 def test_pools16_and_stem_pack(dt):
     from mauv import ops
     N, H, C = 3, 9, 64

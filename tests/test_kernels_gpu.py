@@ -1,5 +1,7 @@
 """Kernel-level parity on the GPU: every libmauv_hip kernel vs a float64 torch-CPU
-reference of the same op (conv fwd/dgrad/wgrad, BN fwd/bwd, pooling, reparam, KL, head).
+reference of the same op (conv fwd/dgrad/wgrad, BN fwd/bwd, pooling, reparam, head).  The KL
+kernels are in tests/test_kl_kernels_gpu.py, the fused Adam kernel's table form in
+tests/test_adam_kernel_gpu.py.
 """
 import math
 
@@ -390,6 +392,22 @@ def test_pools():
     close(dxa, (da.double() / (H * H))[:, None, None, :].expand(N, H, H, C))
 
 
+@pytest.mark.parametrize("shape", list(range(5)))
+def test_maxpool_nonsquare_argmax_ties_nan(shape):
+    """fp32 max-pool on H != W images: pooled values, argmax bytes and dx against torch
+    (tests.helpers.check_maxpool)."""
+    from tests.helpers import POOL_SHAPES, check_maxpool
+    check_maxpool(torch.float32, *POOL_SHAPES[shape], close)
+
+
+@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16, torch.float16],
+                         ids=["fp32", "bf16", "f16"])
+@pytest.mark.parametrize("HW,C", [(1, 5), (49, 5), (1, 2048), (49, 2048)])
+def test_avgpool_shapes(dt, HW, C):
+    from tests.helpers import check_avgpool
+    check_avgpool(dt, 3, HW, C)
+
+
 def test_reparam_and_kl():
     from mauv import ops
     G, Cout, Cin, R = 3, 16, 8, 3
@@ -412,6 +430,32 @@ def test_reparam_and_kl():
     dW = dws.double().sum(0).permute(0, 1, 4, 2, 3)  # [G][Cout][Cin][R][R]
     close(dmu, dW.sum(0))
     close(drho, (dW * eps.double().view(G, Cout, Cin, R, R)).sum(0) * torch.sigmoid(rho.double()))
+    # MOPED-range rho (log(expm1(delta |w|)) reaches -46; 20 is far above any trained value):
+    # the sampler and its backward in units of 2^-24 of the sum of the absolute terms, against
+    # 4x what the fp32 restatement of the same formula errs (floored at 1 unit)
+    u24 = lambda got, ref, mag: ((got.double().cpu() - ref).abs() / (2.0 ** -24 * mag)).max().item()
+    rho2 = torch.empty_like(rho).uniform_(-46.0, 20.0)
+    ops.reparam_sample(mu.to(dev), rho2.to(dev), out, G, 0, 0, 0, Cout, Cin, R * R,
+                       eps=eps.to(dev))
+    e4 = eps.view(G, Cout, Cin, R, R)
+    sig = torch.log1p(torch.exp(rho2.double()))
+    ref = mu.double() + sig * e4.double()
+    mag = mu.double().abs() + sig * e4.double().abs()
+    w32 = mu + torch.log1p(torch.exp(rho2)) * e4
+    got, rest = u24(out.permute(0, 1, 4, 2, 3), ref, mag), u24(w32, ref, mag)
+    print(f"reparam_sample rho in [-46, 20]: {got:.2f} units (fp32 restatement {rest:.2f})")
+    assert got <= 4 * max(1.0, rest)
+    dws1 = torch.randn(1, 1, Cout, R, R, Cin)       # one sample, one slab: a single product
+    dmu.zero_(), drho.zero_()
+    ops.reparam_bwd(dws1.to(dev), 1, mu.to(dev), rho2.to(dev), dmu, drho, 1, 0, 0, 0, Cout, Cin,
+                    R * R, eps=eps[:1].contiguous().to(dev))
+    dW1 = dws1[0, 0].permute(0, 3, 1, 2)
+    assert torch.equal(dmu.cpu(), dW1)
+    ref = dW1.double() * e4[0].double() * torch.sigmoid(rho2.double())
+    r32 = dW1 * e4[0] * (1.0 / (1.0 + torch.exp(-rho2)))
+    got, rest = u24(drho, ref, ref.abs()), u24(r32, ref, ref.abs())
+    print(f"reparam_bwd drho rho in [-46, 20]: {got:.2f} units (fp32 restatement {rest:.2f})")
+    assert got <= 4 * max(1.0, rest)
     # Philox path: G-batched sample == G sequential single-sample draws
     outb = torch.empty(G, Cout, R, R, Cin, device=dev)
     ops.reparam_sample(mu.to(dev), rho.to(dev), outb, G, 42, 10, 7, Cout, Cin, R * R)
