@@ -262,7 +262,8 @@ int mauv_philox_raw(unsigned long long seed, unsigned long long sample, unsigned
 /* ---- fused Adam (adam.hip) ------------------------------------------------------------------
  * torch.optim.Adam as the reference builds it (train/loop_utils.py:45-61: amsgrad=False,
  * maximize=False, L2 weight_decay) stepped for a whole table of fp32 tensors in one launch;
- * step = the (shared) 1-based step count used for bias correction. */
+ * step = the (shared) 1-based step count used for bias correction.  amsgrad, maximize,
+ * decoupled weight decay and several parameter groups: mauv_adam_step_ex below. */
 typedef struct MauvAdamEntry {
   float* param;
   const float* grad;
@@ -287,6 +288,37 @@ typedef struct MauvStepGate {
 } MauvStepGate;
 int mauv_adam_step_gated(const MauvAdamEntry* table, int n, float lr, float beta1, float beta2,
                          float eps, float weight_decay, MauvStepGate* gate, hipStream_t stream);
+/* Every option of torch.optim.Adam's update and several parameter groups in one launch.  A row
+ * names its group (0-based index into `groups`); max_exp_avg_sq is NULL unless that group has
+ * MAUV_ADAM_AMSGRAD.  `groups` is a HOST array of n_groups (1..MAUV_ADAM_MAX_GROUPS) records,
+ * copied into the kernel arguments, so a changed lr needs no device copy.  Element update, in
+ * torch's order: g = -g (MAXIMIZE); p *= 1 - lr wd (DECOUPLED) or g += wd p, when wd != 0;
+ * m += (1 - b1)(g - m); v = b2 v + (1 - b2) g^2; vmax = max(vmax, v) (AMSGRAD);
+ * p -= lr / (1 - b1^t) * m / (sqrt(v or vmax) / sqrt(1 - b2^t) + eps).
+ * gate == NULL: the ungated step at count `step` >= 1.  Otherwise `step` is ignored, the
+ * decision of mauv_adam_step_gated runs first (same modes and counters) and every group steps
+ * at the gate's count with its own lr and betas.  Rows whose group is out of range, or whose
+ * group has AMSGRAD and no max_exp_avg_sq, are left untouched. */
+#define MAUV_ADAM_MAX_GROUPS 8
+#define MAUV_ADAM_AMSGRAD 1u
+#define MAUV_ADAM_MAXIMIZE 2u
+#define MAUV_ADAM_DECOUPLED 4u
+typedef struct MauvAdamEntryEx {
+  float* param;
+  const float* grad;
+  float* exp_avg;
+  float* exp_avg_sq;
+  float* max_exp_avg_sq;
+  long long numel;
+  long long group;
+} MauvAdamEntryEx;
+typedef struct MauvAdamGroup {   /* 32 bytes */
+  float lr, beta1, beta2, eps, weight_decay;
+  unsigned int flags;
+  int reserved[2];
+} MauvAdamGroup;
+int mauv_adam_step_ex(const MauvAdamEntryEx* table, int n, const MauvAdamGroup* groups,
+                      int n_groups, long long step, MauvStepGate* gate, hipStream_t stream);
 
 /* ---- BatchNorm2d (training mode, per MC group) + residual + ReLU (bn.hip) ---------------
  * torchvision Bottleneck bn1..3 / downsample.1 / stem bn1 in .train() for every MC pass

@@ -8,6 +8,8 @@
 // of g per element:
 //   g' = g + wd * p;  m = m + (1 - b1) * (g' - m);  v = b2 * v + (1 - b2) * g'^2
 //   p -= lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
+// mauv_adam_step_ex is the same launch with torch's other options (amsgrad, maximize, decoupled
+// weight decay) and up to 8 parameter groups, each row naming its group.
 #include "mauv_common.h"
 
 using namespace mauv;
@@ -114,6 +116,142 @@ __global__ void step_gate_kernel(MauvStepGate* g, float lr, float beta1, float b
   g->nonfinite = 0;
 }
 
+// ---- every option, several parameter groups (mauv_adam_step_ex) ------------------------------
+// The groups travel by value in the kernel arguments (a StepLR-changed lr needs no device copy);
+// step_size / bc2_sqrt are the host's for the ungated step, formed per block from the gate's
+// count for the gated one.
+struct AdamGroupsArg {
+  MauvAdamGroup g[MAUV_ADAM_MAX_GROUPS];
+  float step_size[MAUV_ADAM_MAX_GROUPS];
+  float bc2_sqrt[MAUV_ADAM_MAX_GROUPS];
+};
+
+struct AdamConsts {
+  float omb1, beta2, omb2, eps, wd, decay, step_size, bc2_sqrt;
+};
+
+// One element of torch's single-tensor Adam with the row's options; all off is adam_elem.
+template <bool AMS, bool MAXI, bool DEC>
+__device__ __forceinline__ void adam_elem_ex(float& p, float g, float& m, float& v, float& vmax,
+                                             const AdamConsts& k) {
+  if (!AMS && !MAXI && !DEC) {
+    adam_elem(p, g, m, v, k.omb1, k.beta2, k.omb2, k.eps, k.wd, k.step_size, k.bc2_sqrt);
+    return;
+  }
+  if (MAXI) g = -g;
+  float ge = g;
+  if (k.wd != 0.f) {
+    if (DEC) p = p * k.decay;
+    else ge = g + k.wd * p;
+  }
+  m = m + k.omb1 * (ge - m);
+  v = v * k.beta2 + k.omb2 * ge * ge;
+  float d = v;
+  if (AMS) {
+    vmax = (v > vmax || v != v) ? v : vmax;   // torch.maximum: a NaN on either side stays
+    d = vmax;
+  }
+  p = p - k.step_size * (m / (sqrtf(d) / k.bc2_sqrt + k.eps));
+}
+
+// The loops of adam_kernel for one row, with a fifth tensor when AMS.
+template <bool AMS, bool MAXI, bool DEC>
+__device__ __forceinline__ void adam_row(const MauvAdamEntryEx& t, long long n4, bool upd,
+                                         bool zero, const AdamConsts& k) {
+  float* grad = const_cast<float*>(t.grad);
+  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+    if (upd) {
+      floatx4 p = ((const floatx4*)t.param)[i];
+      floatx4 g = ((const floatx4*)t.grad)[i];
+      floatx4 m = ((const floatx4*)t.exp_avg)[i];
+      floatx4 v = ((const floatx4*)t.exp_avg_sq)[i];
+      floatx4 x = floatx4{0.f, 0.f, 0.f, 0.f};
+      if (AMS) x = ((const floatx4*)t.max_exp_avg_sq)[i];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float pe = p[e], me = m[e], ve = v[e], xe = x[e];
+        adam_elem_ex<AMS, MAXI, DEC>(pe, g[e], me, ve, xe, k);
+        p[e] = pe; m[e] = me; v[e] = ve; x[e] = xe;
+      }
+      ((floatx4*)t.param)[i] = p;
+      ((floatx4*)t.exp_avg)[i] = m;
+      ((floatx4*)t.exp_avg_sq)[i] = v;
+      if (AMS) ((floatx4*)t.max_exp_avg_sq)[i] = x;
+    }
+    if (zero) ((floatx4*)grad)[i] = floatx4{0.f, 0.f, 0.f, 0.f};
+  }
+  // scalar tail
+  const long long base = n4 * 4;
+  for (long long i = base + blockIdx.x * 256LL + threadIdx.x; i < t.numel;
+       i += (long long)gridDim.x * 256) {
+    if (upd) {
+      float p = t.param[i], m = t.exp_avg[i], v = t.exp_avg_sq[i], x = 0.f;
+      if (AMS) x = t.max_exp_avg_sq[i];
+      adam_elem_ex<AMS, MAXI, DEC>(p, t.grad[i], m, v, x, k);
+      t.param[i] = p;
+      t.exp_avg[i] = m;
+      t.exp_avg_sq[i] = v;
+      if (AMS) t.max_exp_avg_sq[i] = x;
+    }
+    if (zero) grad[i] = 0.f;
+  }
+}
+
+// grid.y = table row, as adam_kernel; the row's group gives the constants and the options,
+// which are uniform over the block: one branch per block, outside the element loops.
+template <bool GATED>
+__global__ __launch_bounds__(256) void adam_ex_kernel(const MauvAdamEntryEx* __restrict__ tab,
+                                                      AdamGroupsArg ga, int n_groups,
+                                                      const MauvStepGate* __restrict__ gate) {
+  int mode = 1;
+  if (GATED) {
+    mode = gate->mode;
+    if (mode == 0) return;
+  }
+  const MauvAdamEntryEx t = tab[blockIdx.y];
+  if (t.group < 0 || t.group >= n_groups) return;
+  const int gi = (int)t.group;
+  const unsigned flags = ga.g[gi].flags & 7u;
+  if ((flags & MAUV_ADAM_AMSGRAD) && !t.max_exp_avg_sq) return;
+  // 16-byte vector path only when all (up to five) tensors are 16-byte aligned
+  const bool aligned = ((reinterpret_cast<uintptr_t>(t.param) | reinterpret_cast<uintptr_t>(t.grad) |
+                         reinterpret_cast<uintptr_t>(t.exp_avg) |
+                         reinterpret_cast<uintptr_t>(t.exp_avg_sq) |
+                         reinterpret_cast<uintptr_t>(t.max_exp_avg_sq)) & 15) == 0;
+  const long long n4 = aligned ? t.numel / 4 : 0;
+  // a block past the row's end (most blocks of a small tensor) has nothing to do
+  const long long first = blockIdx.x * 256LL;
+  if (first >= n4 && n4 * 4 + first >= t.numel) return;
+  const float lr = ga.g[gi].lr, beta1 = ga.g[gi].beta1, wd = ga.g[gi].weight_decay;
+  AdamConsts k;
+  k.beta2 = ga.g[gi].beta2;
+  k.omb1 = 1.0f - beta1;
+  k.omb2 = 1.0f - k.beta2;
+  k.eps = ga.g[gi].eps;
+  k.wd = wd;
+  k.decay = (float)(1.0 - (double)lr * (double)wd);
+  k.step_size = ga.step_size[gi];
+  k.bc2_sqrt = ga.bc2_sqrt[gi];
+  if (GATED && (mode & 1)) {   // as step_gate_kernel forms them, at the gate's count
+    const int st = gate->step;
+    const double bc1 = 1.0 - pow((double)beta1, (double)st);
+    const double bc2 = 1.0 - pow((double)k.beta2, (double)st);
+    k.step_size = (float)((double)lr / bc1);
+    k.bc2_sqrt = (float)sqrt(bc2);
+  }
+  const bool upd = mode & 1, zero = mode & 2;
+  switch (flags) {
+    case 0: adam_row<false, false, false>(t, n4, upd, zero, k); break;
+    case 1: adam_row<true, false, false>(t, n4, upd, zero, k); break;
+    case 2: adam_row<false, true, false>(t, n4, upd, zero, k); break;
+    case 3: adam_row<true, true, false>(t, n4, upd, zero, k); break;
+    case 4: adam_row<false, false, true>(t, n4, upd, zero, k); break;
+    case 5: adam_row<true, false, true>(t, n4, upd, zero, k); break;
+    case 6: adam_row<false, true, true>(t, n4, upd, zero, k); break;
+    default: adam_row<true, true, true>(t, n4, upd, zero, k); break;
+  }
+}
+
 }  // namespace mauv
 
 // One Adam step (bias-correction step index `step` >= 1, shared by the table) for n tensors.
@@ -140,4 +278,40 @@ MAUV_API int mauv_adam_step_gated(const MauvAdamEntry* table, int n, float lr, f
   hipLaunchKernelGGL(adam_kernel<true>, dim3(64, n), dim3(256), 0, stream, table, lr, beta1,
                      beta2, eps, weight_decay, 0.f, 1.f, (const MauvStepGate*)gate);
   return check_launch("adam_step_gated");
+}
+
+// Every Adam option and up to MAUV_ADAM_MAX_GROUPS parameter groups in one launch (mauv.h).
+// gate == NULL: the ungated step at `step`; otherwise the gate's decision runs first, as in
+// mauv_adam_step_gated, and every group steps at the gate's count.
+MAUV_API int mauv_adam_step_ex(const MauvAdamEntryEx* table, int n, const MauvAdamGroup* groups,
+                               int n_groups, long long step, MauvStepGate* gate,
+                               hipStream_t stream) {
+  if (n <= 0 || n > 65535 || !table) { set_error("adam_step_ex: bad table size"); return kErrArg; }
+  if (n_groups < 1 || n_groups > MAUV_ADAM_MAX_GROUPS || !groups) {
+    set_error("adam_step_ex: 1..8 parameter groups");
+    return kErrArg;
+  }
+  if (!gate && step < 1) { set_error("adam_step_ex: ungated step < 1"); return kErrArg; }
+  AdamGroupsArg ga = {};
+  for (int i = 0; i < n_groups; ++i) {
+    ga.g[i] = groups[i];
+    ga.step_size[i] = 0.f;
+    ga.bc2_sqrt[i] = 1.f;
+    if (!gate) {
+      const double bc1 = 1.0 - pow((double)groups[i].beta1, (double)step);
+      const double bc2 = 1.0 - pow((double)groups[i].beta2, (double)step);
+      ga.step_size[i] = (float)(groups[i].lr / bc1);
+      ga.bc2_sqrt[i] = (float)sqrt(bc2);
+    }
+  }
+  if (gate) {
+    hipLaunchKernelGGL(step_gate_kernel, dim3(1), dim3(1), 0, stream, gate, groups[0].lr,
+                       groups[0].beta1, groups[0].beta2);
+    hipLaunchKernelGGL(adam_ex_kernel<true>, dim3(64, n), dim3(256), 0, stream, table, ga,
+                       n_groups, (const MauvStepGate*)gate);
+  } else {
+    hipLaunchKernelGGL(adam_ex_kernel<false>, dim3(64, n), dim3(256), 0, stream, table, ga,
+                       n_groups, nullptr);
+  }
+  return check_launch("adam_step_ex");
 }

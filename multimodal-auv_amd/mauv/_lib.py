@@ -53,6 +53,7 @@ SIGNATURES = {
     # adam.hip
     "mauv_adam_step": [P, I, F, F, F, F, F, LL, P],
     "mauv_adam_step_gated": [P, I, F, F, F, F, F, P, P],
+    "mauv_adam_step_ex": [P, I, P, I, LL, P, P],
     # bn.hip
     "mauv_bn_workspace_floats": [I, LL, I],
     "mauv_bn_fwd_train": [P, I, LL, I, P, P, P, P, F, F, P, P, P, P, P, P, I, P, P],
@@ -115,6 +116,12 @@ class MauvRoute(ctypes.Structure):
     _fields_ = [("f32_math", I), ("halo3", I), ("big16", I), ("big16_min_k", I),
                 ("haloc16", I), ("expand16", I), ("reparam_kernels", I),
                 ("reserved", I * 9)]
+
+
+class MauvAdamGroup(ctypes.Structure):
+    """include/mauv.h MauvAdamGroup: one parameter group of mauv_adam_step_ex (32 bytes)."""
+    _fields_ = [("lr", F), ("beta1", F), ("beta2", F), ("eps", F), ("weight_decay", F),
+                ("flags", U32), ("reserved", I * 2)]
 
 
 class MauvError(RuntimeError):

@@ -125,6 +125,7 @@ class RootState:
             if is_bayesian(m):
                 self.ids[id(m)] = len(self.ids)
         self.params = list(root.parameters())
+        self.trainable = None   # those with requires_grad, listed at the first training step
         self.seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         self.offset = 0
         self.arena = None

@@ -2,7 +2,10 @@
 
 * ``define_optimizers_and_schedulers``      loop_utils.py:13-63 (CE + 4 Adam + 4 StepLR; Adam
                                             is mauv.optim.FusedAdam — one HIP launch per step —
-                                            for models on a ROCm device, torch's otherwise)
+                                            for models on a ROCm device, torch's otherwise;
+                                            optimizer_params[...] go in as keyword arguments,
+                                            amsgrad / maximize / decoupled_weight_decay /
+                                            foreach / fused included, as into torch's Adam)
 * ``train_and_evaluate_unimodal_model``     loop_utils.py:65-159 (epochs ``range(1, n)``)
 * ``train_and_evaluate_multimodal_model``   loop_utils.py:162-250 (scheduler stepped after
                                             training AND after evaluation, as the reference)

@@ -1,41 +1,61 @@
 """FusedAdam — torch.optim.Adam's update for every parameter tensor in one HIP launch.
 
 The reference optimises each model with ``torch.optim.Adam(model.parameters(), lr=...,
-weight_decay=...)`` (train/loop_utils.py:45-61) and steps it after every accepted batch
-(train/multimodal.py:141-143).  ``FusedAdam`` is a drop-in ``torch.optim.Optimizer``: same
-constructor arguments (amsgrad / maximize / capturable are not on the path and are rejected),
-same ``param_groups`` (so ``StepLR`` drives ``lr``), and the same per-parameter state keys
-``step`` / ``exp_avg`` / ``exp_avg_sq`` — its ``state_dict()`` loads into torch.optim.Adam and
-back.  The step is one ``mauv_adam_step`` launch per parameter group over a device table of
-(param, grad, exp_avg, exp_avg_sq, numel) rows; the table is rebuilt only when a pointer
-changes.  Parameters whose ``.grad`` is None are skipped, like torch.
+weight_decay=...)`` (train/loop_utils.py:45-61), forwarding the caller's optimizer options as
+keyword arguments, and steps it after every accepted batch (train/multimodal.py:141-143).
+``FusedAdam`` is a drop-in ``torch.optim.Optimizer``: torch.optim.Adam's constructor arguments
+(``amsgrad``, ``maximize`` and ``decoupled_weight_decay`` change the update; ``foreach`` and
+``fused`` pick torch's implementation, not the maths, and are only kept; ``capturable``,
+``differentiable`` and a tensor ``lr`` / betas are rejected), the same ``param_groups`` keys (so
+``StepLR`` drives ``lr``), and the same per-parameter state keys ``step`` / ``exp_avg`` /
+``exp_avg_sq`` (/ ``max_exp_avg_sq`` with amsgrad) — its ``state_dict()`` loads into
+torch.optim.Adam and back.  ``FusedAdamW`` is the same for torch.optim.AdamW.
+
+One parameter group with the three options off steps through ``mauv_adam_step`` over a device
+table of (param, grad, exp_avg, exp_avg_sq, numel) rows.  Anything else — options, several
+groups — steps through ``mauv_adam_step_ex``: all groups in ONE launch (eight groups per launch),
+rows of (param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq, numel, group) and the groups' lr /
+betas / eps / weight_decay / flags by value.  Tables are rebuilt only when a pointer changes.
+Parameters whose ``.grad`` is None are skipped, like torch.
 
 ``step_gated(gate)`` is the training loop's form (mauv.train.mc_train_step): the decision of
 multimodal.py:133-145 — skip on a non-finite loss, skip the step and the zero_grad on
 non-finite gradients — is read from a device ``MauvStepGate`` by the kernel, and the Adam
-step count lives in that gate, so a training step never waits on the host.
+step count lives in that gate, so a training step never waits on the host.  It covers 1 to 8
+groups over the model's trainable parameters; frozen ones get no state and no step.
 """
+import ctypes
+
 import numpy as np
 import torch
 
 from . import ops  # noqa: F401  (loads the library)
-from ._lib import lib, check
+from ._lib import lib, check, MauvAdamGroup
 
 GATE_WORDS = 16          # sizeof(MauvStepGate) / 4 (include/mauv.h)
 G_OK_LOSS, G_NONFINITE, G_POISONED, G_MODE, G_STEP, G_STEPPED, G_SKIP_LOSS, G_SKIP_GRAD = range(8)
 G_SCRATCH = 15           # a reserved word the training step counts non-finite inputs in
+MAX_GROUPS = 8           # MAUV_ADAM_MAX_GROUPS
+F_AMSGRAD, F_MAXIMIZE, F_DECOUPLED = 1, 2, 4
+EX = "ex"                # key of the all-groups table / fast entry (group 0 alone keeps key 0)
+
+
+def _flags(group):
+    return (F_AMSGRAD if group["amsgrad"] else 0) | (F_MAXIMIZE if group["maximize"] else 0) | \
+        (F_DECOUPLED if group["decoupled_weight_decay"] else 0)
 
 
 class FusedAdam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
-                 amsgrad=False, maximize=False, **unsupported):
-        if amsgrad or maximize:
-            raise ValueError("FusedAdam: amsgrad / maximize are not supported")
+                 amsgrad=False, *, foreach=None, maximize=False, capturable=False,
+                 differentiable=False, fused=None, decoupled_weight_decay=False, **unsupported):
         for k, v in unsupported.items():
             if v not in (None, False):
                 raise ValueError(f"FusedAdam: unsupported option {k}={v}")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
-                                      amsgrad=False, maximize=False))
+                                      amsgrad=amsgrad, maximize=maximize, foreach=foreach,
+                                      capturable=capturable, differentiable=differentiable,
+                                      fused=fused, decoupled_weight_decay=decoupled_weight_decay))
         self._tables = {}
         # per group: the tensors of the last step when every live parameter shared one step
         # count — the next step with the same tensors skips the per-parameter Python work
@@ -47,6 +67,38 @@ class FusedAdam(torch.optim.Optimizer):
         self._gate = None          # device MauvStepGate (int32[16]) of the gated form
         self._gate_dirty = False   # the gate's step count is ahead of state["step"]
         self._gate_params = None
+        self._gate_live = None     # [(parameter, group index)] the gate was built over
+
+    @staticmethod
+    def _check_group(group):
+        """torch.optim.Adam's own range checks, and the options this optimizer does not take."""
+        lr, betas = group["lr"], group["betas"]
+        if isinstance(lr, torch.Tensor) or any(isinstance(b, torch.Tensor) for b in betas):
+            raise ValueError("FusedAdam: a tensor lr / betas is not supported")
+        if group["capturable"] or group["differentiable"]:
+            raise ValueError("FusedAdam: capturable / differentiable are not supported")
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= group["eps"]:
+            raise ValueError(f"Invalid epsilon value: {group['eps']}")
+        for i, b in enumerate(betas):
+            if not 0.0 <= b < 1.0:
+                raise ValueError(f"Invalid beta parameter at index {i}: {b}")
+        if not 0.0 <= group["weight_decay"]:
+            raise ValueError(f"Invalid weight_decay value: {group['weight_decay']}")
+
+    def add_param_group(self, param_group):
+        super().add_param_group(param_group)
+        self._check_group(self.param_groups[-1])
+        if getattr(self, "_gate", None) is not None:   # the gate was built over the old groups
+            self._sync_gate()
+            self._gate = None
+        if hasattr(self, "_fast"):
+            self._fast.pop(EX, None)
+
+    def _simple(self):
+        """One group, amsgrad / maximize / decoupled off: the mauv_adam_step entry points."""
+        return len(self.param_groups) == 1 and _flags(self.param_groups[0]) == 0
 
     def _table(self, gi, live):
         key = tuple((p.data_ptr(), p.grad.data_ptr(), self.state[p]["exp_avg"].data_ptr(),
@@ -63,20 +115,67 @@ class FusedAdam(torch.optim.Optimizer):
         self._tables[gi] = (key, tab)
         return tab
 
+    def _layout(self, pairs):
+        """What an all-groups table depends on besides the pointers: each row's group and every
+        group's option flags (amsgrad adds a column)."""
+        return tuple(gi for _, gi in pairs), tuple(_flags(g) for g in self.param_groups)
+
+    def _table_ex(self, key, pairs):
+        """(device table, launches) over ``pairs`` = [(parameter, group index)] in group order.
+        A launch is (first row, rows, its group indices): at most MAX_GROUPS groups each, a row's
+        group column counting within its launch."""
+        ams = [bool(g["amsgrad"]) for g in self.param_groups]
+        rows = np.zeros((len(pairs), 7), dtype=np.int64)
+        chunks = []
+        for i, (p, gi) in enumerate(pairs):
+            if not chunks or (gi != chunks[-1][2][-1] and len(chunks[-1][2]) == MAX_GROUPS):
+                chunks.append([i, 0, [gi]])
+            elif gi != chunks[-1][2][-1]:
+                chunks[-1][2].append(gi)
+            chunks[-1][1] += 1
+            st = self.state[p]
+            rows[i] = (p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(),
+                       st["exp_avg_sq"].data_ptr(),
+                       st["max_exp_avg_sq"].data_ptr() if ams[gi] else 0, p.numel(),
+                       len(chunks[-1][2]) - 1)
+        ident = (rows.tobytes(), tuple((a, b, tuple(c)) for a, b, c in chunks))
+        cached = self._tables.get(key)
+        if cached is not None and cached[0] == ident:
+            return cached[1]
+        tab = (torch.from_numpy(rows).to(pairs[0][0].device), ident[1])
+        self._tables[key] = (ident, tab)
+        return tab
+
+    def _launch_ex(self, tab, t, gate):
+        """mauv_adam_step_ex over every launch of ``tab``; the groups' current lr, betas, eps,
+        weight_decay and flags travel by value."""
+        table, chunks = tab
+        for r0, n, gis in chunks:
+            arr = (MauvAdamGroup * len(gis))()
+            for a, gi in zip(arr, gis):
+                g = self.param_groups[gi]
+                a.lr, a.eps, a.weight_decay = g["lr"], g["eps"], g["weight_decay"]
+                (a.beta1, a.beta2), a.flags = g["betas"], _flags(g)
+            check(lib.mauv_adam_step_ex(table.data_ptr() + 56 * r0, n, ctypes.addressof(arr),
+                                        len(gis), t, gate, ops.stream()), "adam_step_ex")
+
     def _fast_entry(self, gi, live):
-        """The cached (t, table, step buffer) of group ``gi`` if it is still valid for ``live``."""
+        """The cached (t, table, step buffer) of group ``gi`` (or of all groups, EX) if it is
+        still valid for ``live``."""
         fast = self._fast.get(gi)
         if fast is None:
             return None
-        ptrs, gptrs, moments, state_id, t, tab, steps = fast
+        ptrs, gptrs, moments, state_id, t, tab, steps = fast[:7]
         if state_id != id(self.state) or len(ptrs) != len(live):
             return None
         if [p.data_ptr() for p in live] != ptrs or [p.grad.data_ptr() for p in live] != gptrs:
             return None
         try:
-            for p, (m, v) in zip(live, moments):
+            for p, mom in zip(live, moments):
                 st = self.state[p]
-                if st["exp_avg"] is not m or st["exp_avg_sq"] is not v:
+                if st["exp_avg"] is not mom[0] or st["exp_avg_sq"] is not mom[1]:
+                    return None
+                if len(mom) == 3 and st["max_exp_avg_sq"] is not mom[2]:
                     return None
         except KeyError:
             return None
@@ -94,16 +193,51 @@ class FusedAdam(torch.optim.Optimizer):
                 st["step"] = torch.tensor(0.0)
                 st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                 st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            if group["amsgrad"] and "max_exp_avg_sq" not in st:
+                st["max_exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
 
-    def _remember(self, gi, live, t, tab):
+    def _remember(self, gi, live, t, tab, layout=None):
         # re-home the step counters as 0-dim views of one CPU tensor (still float tensors,
         # torch.optim.Adam-compatible): the fast path bumps them in one op
         buf = torch.full((len(live),), float(t))
         for i, p in enumerate(live):
             self.state[p]["step"] = buf[i]
         moments = [(self.state[p]["exp_avg"], self.state[p]["exp_avg_sq"]) for p in live]
+        if layout is not None:   # every moment tensor the table points at, max_exp_avg_sq too
+            ams = [bool(g["amsgrad"]) for g in self.param_groups]
+            moments = [mom + (self.state[p]["max_exp_avg_sq"],) if ams[row_group] else mom
+                       for p, row_group, mom in zip(live, layout[0], moments)]
         self._fast[gi] = ([p.data_ptr() for p in live], [p.grad.data_ptr() for p in live],
-                          moments, id(self.state), t, tab, buf)
+                          moments, id(self.state), t, tab, buf) + \
+            (() if layout is None else (layout,))
+
+    def _step_ex(self):
+        """The ungated step of anything but one plain group: every group with live parameters
+        in one launch (per shared step count, MAX_GROUPS groups per launch)."""
+        pairs = [(p, gi) for gi, g in enumerate(self.param_groups) for p in g["params"]
+                 if p.grad is not None]
+        if not pairs:
+            return
+        live, layout = [p for p, _ in pairs], self._layout(pairs)
+        fast = self._fast_entry(EX, live)
+        if fast is not None and fast[7] == layout:
+            t = fast[4] + 1
+            fast[6].add_(1.0)   # every live parameter's state["step"] is a view of it
+            self._launch_ex(fast[5], t, None)
+            self._fast[EX] = fast[:4] + (t,) + fast[5:]
+            return
+        self._fast.pop(EX, None)
+        for gi, group in enumerate(self.param_groups):
+            self._prepare(EX, group, [p for p, g in pairs if g == gi])
+        steps = {}
+        for p, gi in pairs:
+            self.state[p]["step"] += 1
+            steps.setdefault(int(self.state[p]["step"].item()), []).append((p, gi))
+        for t, ps in steps.items():
+            tab = self._table_ex((EX, t) if len(steps) > 1 else EX, ps)
+            self._launch_ex(tab, t, None)
+            if len(steps) == 1:
+                self._remember(EX, live, t, tab, layout)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -113,6 +247,9 @@ class FusedAdam(torch.optim.Optimizer):
                 loss = closure()
         self._sync_gate()
         self._gate = None   # an ungated step moves the count on the host: re-read it next time
+        if not self._simple():
+            self._step_ex()
+            return loss
         for gi, group in enumerate(self.param_groups):
             live = [p for p in group["params"] if p.grad is not None]
             if not live:
@@ -147,19 +284,24 @@ class FusedAdam(torch.optim.Optimizer):
 
     # ---- the device-gated form ---------------------------------------------------------------
     def gate(self, params, device):
-        """The device MauvStepGate for a training loop over ``params`` (the model's parameters),
-        or None when the gated form does not apply: one parameter group holding exactly those
-        tensors, all sharing one step count."""
+        """The device MauvStepGate for a training loop over ``params`` (the model's trainable
+        parameters), or None when the gated form does not apply: 1 to 8 parameter groups whose
+        parameters with requires_grad are exactly those tensors, all sharing one step count,
+        and whose other parameters are frozen and hold no gradient."""
         if self._gate is not None and self._gate_params is params and \
                 self._gate.device == torch.device(device):
             return self._gate
-        if len(self.param_groups) != 1:
+        if not 1 <= len(self.param_groups) <= MAX_GROUPS:
             return None
-        gp = self.param_groups[0]["params"]
+        pairs = [(p, gi) for gi, g in enumerate(self.param_groups) for p in g["params"]]
+        if any(p.grad is not None for p, _ in pairs if not p.requires_grad):
+            return None
+        pairs = [(p, gi) for p, gi in pairs if p.requires_grad]
+        gp = [p for p, _ in pairs]
         if len(gp) != len(params) or {id(p) for p in gp} != {id(p) for p in params}:
             return None
         if self._gate is None or self._gate.device != torch.device(device):
-            counts = {int(self.state[p]["step"].item()) if "step" in self.state[p] else 0
+            counts = {int(self.state[p]["step"].item()) if "step" in self.state.get(p, ()) else 0
                       for p in gp}
             if len(counts) != 1:
                 return None
@@ -182,34 +324,53 @@ class FusedAdam(torch.optim.Optimizer):
             self._gate = g.to(device)
             self._gate_dirty = False
         self._gate_params = params
+        self._gate_live = pairs
         return self._gate
 
     @torch.no_grad()
     def step_gated(self, gate):
         """One step whose execution (step + zero_grad, restore, or nothing) the kernel reads
-        from ``gate`` — no host synchronisation.  Every parameter of the group must hold a
-        gradient (the model's arena views)."""
+        from ``gate`` — no host synchronisation.  Every trainable parameter of every group must
+        hold a gradient (the model's arena views); frozen ones get no state and no step."""
         assert gate is self._gate, "step_gated: use the gate returned by FusedAdam.gate()"
-        group = self.param_groups[0]
-        live = group["params"]
+        pairs = self._gate_live
+        live = [p for p, _ in pairs]
         if any(p.grad is None for p in live):
             raise RuntimeError("step_gated: every parameter needs a gradient tensor")
-        b1, b2 = group["betas"]
-        fast = self._fast_entry(0, live)
-        if fast is None:
-            self._prepare(0, group, live)
-            tab = self._table(0, live)
-            t = int(self._gate_step_host())
-            self._remember(0, live, t, tab)
-            fast = self._fast[0]
+        simple = self._simple()
+        if simple:
+            group = self.param_groups[0]
+            b1, b2 = group["betas"]
+            fast = self._fast_entry(0, live)
+            if fast is None:
+                self._prepare(0, group, live)
+                tab = self._table(0, live)
+                t = int(self._gate_step_host())
+                self._remember(0, live, t, tab)
+                fast = self._fast[0]
+        else:
+            layout = self._layout(pairs)
+            fast = self._fast_entry(EX, live)
+            if fast is None or fast[7] != layout:
+                self._fast.pop(EX, None)
+                for gi, group in enumerate(self.param_groups):
+                    self._prepare(EX, group, [p for p, g in pairs if g == gi])
+                tab = self._table_ex(EX, pairs)
+                assert len(tab[1]) == 1   # gate() takes at most MAX_GROUPS groups
+                t = int(self._gate_step_host())
+                self._remember(EX, live, t, tab, layout)
+                fast = self._fast[EX]
         tab = fast[5]
         from torch.optim import optimizer as _topt
         for hook in list(_topt._global_optimizer_pre_hooks.values()) + \
                 list(self._optimizer_step_pre_hooks.values()):
             hook(self, (self,), {})
-        check(lib.mauv_adam_step_gated(tab.data_ptr(), len(live), group["lr"], b1, b2,
-                                       group["eps"], group["weight_decay"], gate.data_ptr(),
-                                       ops.stream()), "adam_step_gated")
+        if simple:
+            check(lib.mauv_adam_step_gated(tab.data_ptr(), len(live), group["lr"], b1, b2,
+                                           group["eps"], group["weight_decay"], gate.data_ptr(),
+                                           ops.stream()), "adam_step_gated")
+        else:
+            self._launch_ex(tab, 0, gate.data_ptr())
         self._gate_dirty = True
         # what torch.optim.Optimizer.step's wrapper records: an LR scheduler stepped after this
         # does not warn "lr_scheduler.step() before optimizer.step()"; step hooks still run
@@ -228,12 +389,15 @@ class FusedAdam(torch.optim.Optimizer):
         if self._gate is None or not self._gate_dirty:
             return
         t = self._gate_step_host()
-        for p in self.param_groups[0]["params"]:
-            if "step" in self.state[p]:
-                self.state[p]["step"].fill_(float(t))
-        fast = self._fast.get(0)
-        if fast is not None:
-            self._fast[0] = fast[:4] + (t,) + fast[5:]
+        for group in self.param_groups:
+            for p in group["params"]:
+                st = self.state.get(p)   # (a frozen parameter has none, and gets none here)
+                if st is not None and "step" in st:
+                    st["step"].fill_(float(t))
+        for key in (0, EX):
+            fast = self._fast.get(key)
+            if fast is not None:
+                self._fast[key] = fast[:4] + (t,) + fast[5:]
         self._gate_dirty = False
 
     def state_dict(self):
@@ -243,7 +407,23 @@ class FusedAdam(torch.optim.Optimizer):
     def load_state_dict(self, state_dict):
         """torch's load (new state tensors, step counts): the cached tables are dropped."""
         super().load_state_dict(state_dict)
+        for group in self.param_groups:   # a state_dict saved before these keys existed
+            for k, v in self.defaults.items():
+                group.setdefault(k, v)
+            self._check_group(group)
         self._tables.clear()
         self._fast.clear()
         self._gate = None
         self._gate_dirty = False
+
+
+class FusedAdamW(FusedAdam):
+    """torch.optim.AdamW: FusedAdam with decoupled weight decay (default 1e-2); its
+    ``state_dict()`` loads into torch.optim.AdamW and back."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
+                 amsgrad=False, **options):
+        if not options.pop("decoupled_weight_decay", True):
+            raise ValueError("FusedAdamW: decoupled_weight_decay is always on")
+        super().__init__(params, lr, betas, eps, weight_decay, amsgrad,
+                         decoupled_weight_decay=True, **options)

@@ -143,14 +143,19 @@ def mc_loss(model, inputs_tuple, labels, criterion, num_mc, batch_size, kl_w):
 
 def _step_gate(model, optimizer, loss):
     """The device MauvStepGate when the batch can be decided on the device: a mauv engine model
-    whose gradients live in its arena, stepped by FusedAdam over exactly its parameters."""
+    whose gradients live in its arena, stepped by FusedAdam over exactly its trainable
+    parameters (frozen ones may sit in the optimizer; they are never stepped)."""
     from .optim import FusedAdam
     if not isinstance(optimizer, FusedAdam) or not loss.is_cuda:
         return None
     st = unwrap(model).__dict__.get("_mauv_state")
-    if st is None or not all(p.requires_grad for p in st.params):
+    if st is None:
         return None
-    return optimizer.gate(st.params, loss.device)
+    if st.trainable is None:   # one list: gate() compares identity
+        st.trainable = [p for p in st.params if p.requires_grad]
+    if not st.trainable:
+        return None
+    return optimizer.gate(st.trainable, loss.device)
 
 
 def _batch_finite(loss, inputs_tuple, counter=None):
