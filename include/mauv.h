@@ -76,6 +76,19 @@ typedef struct MauvRoute {
 int mauv_get_route(MauvRoute* out);
 int mauv_set_route(const MauvRoute* in);
 
+/* ---- conv geometry (every mauv_conv2d_* entry point and sizing helper, fp32 and 16-bit) ----
+ * Accepted, and tested against float64 per kernel family (tests/test_conv_rect_gpu.py): filter
+ * rows R and columns S independent (R != S), image height H and width W independent (H != W),
+ * one stride >= 1 and one zero padding pad >= 0 for both axes (pad may exceed R / 2 or S / 2:
+ * outputs over padding only are 0 + bias), Ho = (H + 2 pad - R) / stride + 1 and Wo likewise
+ * from W and S.  Weights are [G][Cout][R][S][Cin], weight-gradient slabs
+ * [splits][G][Cout][R*S*Cin] with columns in (r, s, c) order.
+ * Refused with a negative code before anything is computed or launched, mauv_last_error() naming
+ * the entry point and the quantity: G, B, H, W, Cin, Cout, R, S or stride < 1; pad < 0; a filter
+ * taller or wider than the padded image (Ho < 1 or Wo < 1); splits < 1 (weight gradients).  The
+ * sizing helpers return that code in place of a count.  Not expressible: per-axis stride or
+ * padding, dilation, groups, padding modes other than zeros. */
+
 /* ---- implicit-GEMM convolution on MFMA (conv_gemm.hip) ---------------------------------
  * Replaces F.conv2d inside bayesian-torch Conv2dReparameterization.forward for every conv of
  * the three torchvision ResNet-50 trunks (models/base_models.py:15-18,

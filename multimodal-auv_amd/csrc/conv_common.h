@@ -162,6 +162,42 @@ bool conv_fwd_batch_chunks(const ConvArgs& a0, long long lim, int esz, F launch)
   return true;
 }
 
+// ---- host: geometry check of every conv entry point and sizing helper (include/mauv.h) ----
+// 0, or kErrArg with mauv_last_error() = "<what>: <quantity> must be ..., got <value>": every
+// extent, R, S and stride at least 1, pad at least 0, the filter inside the padded image (Ho, Wo
+// at least 1) and, for the weight gradients, splits at least 1 (the sizing helpers and the other
+// entry points pass splits = 1).  Runs before any arithmetic on its arguments: stride 0 and
+// splits 0 are divisors.
+inline int conv_check_geometry(const char* what, int G, int B, int H, int W, int Cin, int Cout,
+                               int R, int S, int stride, int pad, int splits = 1) {
+  const struct { const char* name; int v, lo; } q[] = {
+      {"G", G, 1}, {"B", B, 1}, {"H", H, 1}, {"W", W, 1}, {"Cin", Cin, 1}, {"Cout", Cout, 1},
+      {"R", R, 1}, {"S", S, 1}, {"stride", stride, 1}, {"pad", pad, 0}, {"splits", splits, 1}};
+  for (const auto& e : q)
+    if (e.v < e.lo) {
+      set_error(std::string(what) + ": " + e.name + " must be >= " + std::to_string(e.lo) +
+                ", got " + std::to_string(e.v));
+      return kErrArg;
+    }
+  // (64-bit: H + 2 pad may pass INT_MAX; a negative numerator is no output row, not the one
+  // that the truncating division would give)
+  const long long nh = (long long)H + 2LL * pad - R, nw = (long long)W + 2LL * pad - S;
+  const long long Ho = nh < 0 ? 0 : nh / stride + 1, Wo = nw < 0 ? 0 : nw / stride + 1;
+  if (Ho < 1) {
+    set_error(std::string(what) + ": Ho must be >= 1, got " + std::to_string(Ho) + " (H = " +
+              std::to_string(H) + ", R = " + std::to_string(R) + ", pad = " + std::to_string(pad) +
+              ": the filter is taller than the padded image)");
+    return kErrArg;
+  }
+  if (Wo < 1) {
+    set_error(std::string(what) + ": Wo must be >= 1, got " + std::to_string(Wo) + " (W = " +
+              std::to_string(W) + ", S = " + std::to_string(S) + ", pad = " + std::to_string(pad) +
+              ": the filter is wider than the padded image)");
+    return kErrArg;
+  }
+  return 0;
+}
+
 // ---- host: the argument block of the C entry points (conv_gemm.hip, conv_gemm16.hip) ----
 // geometry, x strides (xs: {group, batch, h, w, c} in elements, NULL = dense NHWC) and weight
 // stride of one conv; the entry point adds pointers and GEMM dims

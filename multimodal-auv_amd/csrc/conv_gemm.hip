@@ -601,7 +601,7 @@ MAUV_API int mauv_conv2d_fwd_f32(const float* x, const long long* x_strides,
                                  int H, int W, int Cin, int Cout, int R, int S, int stride,
                                  int pad, float* st_mean, float* st_m2, float* st_cnt,
                                  hipStream_t stream) {
-  if (G <= 0 || B <= 0 || Cin <= 0 || Cout <= 0) { set_error("conv2d_fwd: bad shape"); return kErrArg; }
+  if (int e = conv_check_geometry("conv2d_fwd_f32", G, B, H, W, Cin, Cout, R, S, stride, pad)) return e;
   ConvArgs a = make_args(G, B, H, W, Cin, Cout, R, S, stride, pad, x_strides);
   a.x = x; a.w = w; a.out = y; a.bias = bias; a.bias_sg = Cout;
   a.xsc = x_scale; a.xsh = x_shift; a.xrelu = x_relu;
@@ -659,6 +659,7 @@ MAUV_API int mauv_conv2d_bwd_data_f32(const float* dy, const float* w, float* dx
                                       const float* bn_scale, const float* bn_shift,
                                       const float* bn_mean, const float* bn_invstd, int bn_relu,
                                       float* bn_p1, float* bn_p2, hipStream_t stream) {
+  if (int e = conv_check_geometry("conv2d_bwd_data_f32", G, B, H, W, Cin, Cout, R, S, stride, pad)) return e;
   ConvArgs a = make_args(G, B, H, W, Cin, Cout, R, S, stride, pad, nullptr);
   a.dy = dy; a.w = w; a.out = dx; a.addend = addend; a.accumulate = accumulate;
   a.add_mask = addend ? addend_mask : nullptr;
@@ -691,11 +692,13 @@ MAUV_API int mauv_conv2d_bwd_data_f32(const float* dy, const float* w, float* dx
 // Number of per-m-tile BN statistic partials the fused epilogues write (host sizing helpers).
 MAUV_API int mauv_conv2d_fwd_stat_blocks(int G, int B, int H, int W, int Cin, int Cout, int R,
                                          int S, int stride, int pad) {
+  if (int e = conv_check_geometry("conv2d_fwd_stat_blocks", G, B, H, W, Cin, Cout, R, S, stride, pad)) return e;
   const int Ho = (H + 2 * pad - R) / stride + 1, Wo = (W + 2 * pad - S) / stride + 1;
   return stat_blocks(B * Ho * Wo);
 }
 MAUV_API int mauv_conv2d_bwd_data_stat_blocks(int G, int B, int H, int W, int Cin, int Cout,
                                               int R, int S, int stride, int pad) {
+  if (int e = conv_check_geometry("conv2d_bwd_data_stat_blocks", G, B, H, W, Cin, Cout, R, S, stride, pad)) return e;
   return dgrad_stat_blocks(B, H, W, stride);
 }
 
@@ -703,6 +706,7 @@ MAUV_API int mauv_conv2d_bwd_data_stat_blocks(int G, int B, int H, int W, int Ci
 // can size the partial-slab workspace: splits * G * Cout * R*S*Cin floats).
 MAUV_API int mauv_conv2d_wgrad_splits(int G, int B, int H, int W, int Cin, int Cout, int R,
                                       int S, int stride, int pad) {
+  if (int e = conv_check_geometry("conv2d_wgrad_splits", G, B, H, W, Cin, Cout, R, S, stride, pad)) return e;
   const int Ho = (H + 2 * pad - R) / stride + 1, Wo = (W + 2 * pad - S) / stride + 1;
   const long long P = (long long)B * Ho * Wo;
   const int N = R * S * Cin;
@@ -765,6 +769,7 @@ MAUV_API int mauv_conv2d_bwd_weight_f32(const float* x, const long long* x_strid
                                         const float* dy, float* ws, int splits, int G, int B,
                                         int H, int W, int Cin, int Cout, int R, int S,
                                         int stride, int pad, hipStream_t stream) {
+  if (int e = conv_check_geometry("conv2d_bwd_weight_f32", G, B, H, W, Cin, Cout, R, S, stride, pad, splits)) return e;
   ConvArgs a = make_args(G, B, H, W, Cin, Cout, R, S, stride, pad, x_strides);
   a.x = x; a.dy = dy; a.out = ws;
   a.xsc = x_scale; a.xsh = x_shift; a.xrelu = x_relu;

@@ -332,6 +332,7 @@ MAUV_API int mauv_conv2d_fwd_h16(int dtype, const void* x, const long long* x_st
                                  int Cout, int R, int S, int stride, int pad, float* st_mean,
                                  float* st_m2, float* st_cnt, const float* y_shift,
                                  hipStream_t stream) {
+  if (int e = conv_check_geometry("conv2d_fwd_h16", G, B, H, W, Cin, Cout, R, S, stride, pad)) return e;
   if (int e = check_shape16("conv2d_fwd_h16", dtype, G, B, Cin, Cout, x_strides)) return e;
   if (!aligned16(x) || !aligned16(w)) { set_error("conv2d_fwd_h16: x, w must be 16-B aligned"); return kErrArg; }
   ConvArgs a = make_args(G, B, H, W, Cin, Cout, R, S, stride, pad, x_strides);
@@ -413,6 +414,7 @@ MAUV_API int mauv_conv2d_bwd_data_h16(int dtype, const void* dy, const void* w, 
                                       const void* addend, int accumulate, int G, int B, int H,
                                       int W, int Cin, int Cout, int R, int S, int stride, int pad,
                                       hipStream_t stream) {
+  if (int e = conv_check_geometry("conv2d_bwd_data_h16", G, B, H, W, Cin, Cout, R, S, stride, pad)) return e;
   return mauv_conv2d_bwd_data_bn_h16(dtype, dy, w, dx, addend, accumulate, G, B, H, W, Cin, Cout,
                                      R, S, stride, pad, nullptr, nullptr, nullptr, nullptr,
                                      nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr,
@@ -436,6 +438,7 @@ MAUV_API int mauv_conv2d_bwd_data_bn_h16(int dtype, const void* dy, const void* 
                                          const float* bn_shift, const float* bn_mean,
                                          const float* bn_invstd, int bn_relu, float* bn_p1,
                                          float* bn_p2, hipStream_t stream) {
+  if (int e = conv_check_geometry("conv2d_bwd_data_bn_h16", G, B, H, W, Cin, Cout, R, S, stride, pad)) return e;
   if (int e = check_shape16("conv2d_bwd_data_h16", dtype, G, B, Cin, Cout, nullptr)) return e;
   if (Cout % HBK) { set_error("conv2d_bwd_data_h16: needs Cout % 32 == 0"); return kErrArg; }
   const bool bst = bn_p1 != nullptr;
@@ -483,6 +486,7 @@ MAUV_API int mauv_conv2d_bwd_weight_h16(int dtype, const void* x, const long lon
                                         const void* dy, float* ws, int splits, int G, int B,
                                         int H, int W, int Cin, int Cout, int R, int S, int stride,
                                         int pad, hipStream_t stream) {
+  if (int e = conv_check_geometry("conv2d_bwd_weight_h16", G, B, H, W, Cin, Cout, R, S, stride, pad, splits)) return e;
   if (int e = check_shape16("conv2d_bwd_weight_h16", dtype, G, B, Cin, Cout, x_strides)) return e;
   ConvArgs a = make_args(G, B, H, W, Cin, Cout, R, S, stride, pad, x_strides);
   a.x = (const float*)x; a.dy = (const float*)dy; a.out = ws;

@@ -22,6 +22,20 @@ def _pair(v):
     return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
 
 
+def _square(name, v):
+    """A conv geometry argument as its one value: an int, or a pair of two equal ints.  The
+    engine runs square filters with one stride and one padding for both axes; anything else is
+    refused here (by name) rather than applied as its first element."""
+    if isinstance(v, str):
+        raise NotImplementedError(f"mauv: Conv2dReparameterization {name}={v!r}: string {name} "
+                                  "modes are not on the path (give the zero padding as an int)")
+    p = _pair(v)
+    if len(p) != 2 or p[0] != p[1]:
+        raise NotImplementedError(f"mauv: Conv2dReparameterization {name}={v!r}: only an int or "
+                                  f"an equal pair is on the path (rectangular {name} is not)")
+    return int(p[0])
+
+
 class _BayesBase(nn.Module):
     # prior sigma/mean are scalars (bayesian-torch fills weight-shaped non-persistent buffers
     # with these constants; nothing else reads them, so no per-element buffers are kept)
@@ -53,8 +67,9 @@ class Conv2dReparameterization(_BayesBase):
         if groups != 1 or _pair(dilation) != (1, 1):
             raise NotImplementedError("mauv: grouped / dilated Bayesian convs are not on the path")
         self.in_channels, self.out_channels = in_channels, out_channels
-        self.kernel_size = kernel_size if isinstance(kernel_size, int) else kernel_size[0]
-        self.stride, self.padding = _pair(stride), _pair(padding)
+        self.kernel_size = _square("kernel_size", kernel_size)
+        self.stride = _pair(_square("stride", stride))
+        self.padding = _pair(_square("padding", padding))
         self.dilation, self.groups = _pair(dilation), groups
         self.bias = bias
         self._init_prior(prior_mean, prior_variance, posterior_mu_init, posterior_rho_init)
@@ -135,8 +150,11 @@ def get_rho(sigma, delta):
 
 
 def _bnn_conv_layer(params, d):
+    if getattr(d, "padding_mode", "zeros") != "zeros":
+        raise NotImplementedError(f"mauv: dnn_to_bnn of a conv with padding_mode="
+                                  f"{d.padding_mode!r}: only zero padding is on the path")
     layer = Conv2dReparameterization(
-        in_channels=d.in_channels, out_channels=d.out_channels, kernel_size=d.kernel_size[0],
+        in_channels=d.in_channels, out_channels=d.out_channels, kernel_size=d.kernel_size,
         stride=d.stride, padding=d.padding, dilation=d.dilation, groups=d.groups,
         prior_mean=params["prior_mu"], prior_variance=params["prior_sigma"],
         posterior_mu_init=params["posterior_mu_init"],

@@ -59,6 +59,16 @@ def out_hw(H, R, stride, pad):
     return (H + 2 * pad - R) // stride + 1
 
 
+def _rs(R):
+    """Filter extents (R, S) = (rows, columns) of a conv wrapper's ``R``: an int is the square
+    R x R filter, a pair is (R, S)."""
+    if isinstance(R, (tuple, list)):
+        if len(R) != 2:
+            raise ValueError(f"a filter size is an int or a pair (R, S), got {R!r}")
+        return int(R[0]), int(R[1])
+    return int(R), int(R)
+
+
 # ----------------------------------------------------------------------- profiling hook
 # bench.py sets PROFILE to a list to time every implicit-GEMM launch with HIP events on the
 # stream the kernel runs on (torch's current stream); entries: (kind, flops, bytes, launches,
@@ -181,7 +191,8 @@ def set_reparam_kernels(sample_blk=None, bwd4=None):
 
 def conv2d_fwd(x, w, y, G, B, H, W, Cin, Cout, R, stride, pad, bias=None, x_strides=None,
                x_bn=None, stats=None, alg_cin=None, ysh=None):
-    """y[G][B*Ho*Wo][Cout] = conv(x'[g], w[g]) (+ bias[g]); w: [G][Cout][R][R][Cin].
+    """y[G][B*Ho*Wo][Cout] = conv(x'[g], w[g]) (+ bias[g]); w: [G][Cout][R][S][Cin].
+    R: the filter side (square), or a pair (R, S) of filter rows and columns.
     x_bn = (scale [G][Cin], shift [G][Cin], relu): x' = [relu](x*scale + shift) on load.
     stats = (mean, m2, cnt) partial buffers for the epilogue BN statistics (see
     fwd_stat_blocks).  ysh ([Cout] fp32, 16-bit only): y is stored centred, y - ysh, and the
@@ -190,13 +201,14 @@ def conv2d_fwd(x, w, y, G, B, H, W, Cin, Cout, R, stride, pad, bias=None, x_stri
     xs = None if x_strides is None else _LL5(*x_strides)
     sc, sh, rl = x_bn if x_bn is not None else (None, None, 0)
     sm, s2, sn = stats if stats is not None else (None, None, None)
-    Ho, Wo = out_hw(H, R, stride, pad), out_hw(W, R, stride, pad)
+    Rr, Ss = _rs(R)
+    Ho, Wo = out_hw(H, Rr, stride, pad), out_hw(W, Ss, stride, pad)
     xg = 1 if (x_strides is not None and x_strides[0] == 0) else G
     # profiling counts ALGORITHMIC work: a zero-padded stem input (16-bit path) counts its
     # real channels (alg_cin)
-    fl = 2.0 * G * B * Ho * Wo * Cout * R * R * (alg_cin or Cin)
+    fl = 2.0 * G * B * Ho * Wo * Cout * Rr * Ss * (alg_cin or Cin)
     esz = w.element_size()
-    nb = esz * (xg * B * H * W * Cin + G * Cout * R * R * Cin + G * B * Ho * Wo * Cout)
+    nb = esz * (xg * B * H * W * Cin + G * Cout * Rr * Ss * Cin + G * B * Ho * Wo * Cout)
     if ysh is not None and w.dtype not in H16:
         raise ValueError("conv2d_fwd: ysh (centred storage) is for the 16-bit convs")
     if w.dtype in H16:
@@ -209,7 +221,7 @@ def conv2d_fwd(x, w, y, G, B, H, W, Cin, Cout, R, stride, pad, bias=None, x_stri
         with _Prof("fwd_" + str(w.dtype)[6:], fl, nb,
                    info=(G, B, H, W, Cin, Cout, R, stride, pad, x_bn is not None)):
             check(lib.mauv_conv2d_fwd_h16(H16[w.dtype], _p(x), xs, _p(sc), _p(sh), int(rl), _p(w),
-                                          _p(y), G, B, H, W, Cin, Cout, R, R, stride, pad,
+                                          _p(y), G, B, H, W, Cin, Cout, Rr, Ss, stride, pad,
                                           _p(sm), _p(s2), _p(sn), _p(ysh), stream()),
                   "conv2d_fwd_h16")
         return
@@ -217,7 +229,7 @@ def conv2d_fwd(x, w, y, G, B, H, W, Cin, Cout, R, stride, pad, bias=None, x_stri
     assert x.is_cuda and x.dtype == torch.float32 and x.device.index == torch.cuda.current_device()
     with _Prof("fwd", fl, nb, info=(G, B, H, W, Cin, Cout, R, stride, pad, x_bn is not None)):
         check(lib.mauv_conv2d_fwd_f32(_p(x), xs, _p(sc), _p(sh), int(rl), _p(w), _p(bias), _p(y),
-                                      G, B, H, W, Cin, Cout, R, R, stride, pad, _p(sm), _p(s2),
+                                      G, B, H, W, Cin, Cout, Rr, Ss, stride, pad, _p(sm), _p(s2),
                                       _p(sn), stream()), "conv2d_fwd")
 
 
@@ -257,12 +269,23 @@ def conv2d_fwd_fold(y, scale, shift, res, res_bn, out, w, y1, G, B, H, W, Cin, C
     return True
 
 
+def _count(n, what):
+    """A sizing helper's count; a negative value is the library's refusal of the geometry."""
+    if n < 0:
+        check(n, what)
+    return n
+
+
 def fwd_stat_blocks(G, B, H, W, Cin, Cout, R, stride, pad):
-    return lib.mauv_conv2d_fwd_stat_blocks(G, B, H, W, Cin, Cout, R, R, stride, pad)
+    """Statistics partials per MC group that conv2d_fwd's epilogue writes (R: int or (R, S))."""
+    return _count(lib.mauv_conv2d_fwd_stat_blocks(G, B, H, W, Cin, Cout, *_rs(R), stride, pad),
+                  "conv2d_fwd_stat_blocks")
 
 
 def dgrad_stat_blocks(G, B, H, W, Cin, Cout, R, stride, pad):
-    return lib.mauv_conv2d_bwd_data_stat_blocks(G, B, H, W, Cin, Cout, R, R, stride, pad)
+    """BN-backward partials per MC group that conv2d_bwd_data's epilogue writes."""
+    return _count(lib.mauv_conv2d_bwd_data_stat_blocks(G, B, H, W, Cin, Cout, *_rs(R), stride,
+                                                       pad), "conv2d_bwd_data_stat_blocks")
 
 
 def conv2d_bwd_data(dy, w, dx, G, B, H, W, Cin, Cout, R, stride, pad, addend=None,
@@ -275,22 +298,23 @@ def conv2d_bwd_data(dy, w, dx, G, B, H, W, Cin, Cout, R, stride, pad, addend=Non
         _dev(torch.uint8, addend_mask)
         if addend is None or addend_mask.numel() * 8 != dx.numel():
             raise ValueError("conv2d_bwd_data: addend_mask needs an addend and dx.numel()/8 bytes")
-    Ho, Wo = out_hw(H, R, stride, pad), out_hw(W, R, stride, pad)
+    Rr, Ss = _rs(R)
+    Ho, Wo = out_hw(H, Rr, stride, pad), out_hw(W, Ss, stride, pad)
     b = bn or {}
-    fl = 2.0 * G * B * Ho * Wo * Cout * R * R * Cin
-    nb = w.element_size() * (G * B * Ho * Wo * Cout + G * Cout * R * R * Cin +
+    fl = 2.0 * G * B * Ho * Wo * Cout * Rr * Ss * Cin
+    nb = w.element_size() * (G * B * Ho * Wo * Cout + G * Cout * Rr * Ss * Cin +
                              G * B * H * W * Cin * (1 + (addend is not None) + bool(accumulate)))
     # kernel launches: one per output-parity class with pixels, except the tapless classes of an
     # accumulating call without addend or partials (they add nothing and are not launched:
     # the stride-2 1x1 downsample's 3 of 4, conv_gemm.hip / conv_gemm16.hip)
     skip_tapless = bool(accumulate) and addend is None and bn is None
 
-    def taps(p):
+    def taps(p, n):
         r0 = (p + pad) % stride
-        return (R - r0 + stride - 1) // stride if r0 < R else 0
+        return (n - r0 + stride - 1) // stride if r0 < n else 0
     nl = sum(1 for ph in range(stride) for pw in range(stride)
              if (H - ph + stride - 1) // stride > 0 and (W - pw + stride - 1) // stride > 0
-             and not (skip_tapless and taps(ph) * taps(pw) == 0))
+             and not (skip_tapless and taps(ph, Rr) * taps(pw, Ss) == 0))
     if w.dtype in H16:
         _h16(w.dtype, dy, w, dx, addend, b.get("y"), b.get("out"))
         _f32(b.get("scale"), b.get("shift"), b.get("mean"), b.get("invstd"), b.get("p1"),
@@ -305,7 +329,7 @@ def conv2d_bwd_data(dy, w, dx, G, B, H, W, Cin, Cout, R, stride, pad, addend=Non
                          (addend is not None, bool(accumulate), addend_mask is not None))):
             check(lib.mauv_conv2d_bwd_data_bn_h16(
                 H16[w.dtype], _p(dy), _p(w), _p(dx), _p(addend), int(accumulate), G, B, H, W,
-                Cin, Cout, R, R, stride, pad, _p(addend_mask), _p(b.get("y")), _p(b.get("out")),
+                Cin, Cout, Rr, Ss, stride, pad, _p(addend_mask), _p(b.get("y")), _p(b.get("out")),
                 _p(mk),
                 _p(b.get("scale")), _p(b.get("shift")), _p(b.get("mean")), _p(b.get("invstd")),
                 int(b.get("relu", 0)), _p(b.get("p1")), _p(b.get("p2")), stream()),
@@ -326,24 +350,28 @@ def conv2d_bwd_data(dy, w, dx, G, B, H, W, Cin, Cout, R, stride, pad, addend=Non
                                             addend_mask is not None))):
         check(lib.mauv_conv2d_bwd_data_f32(
             _p(dy), _p(w), _p(dx), _p(addend), _p(addend_mask), int(accumulate), G, B, H, W,
-            Cin, Cout, R, R,
+            Cin, Cout, Rr, Ss,
             stride, pad, _p(b.get("y")), _p(b.get("out")), _p(b.get("mask")), _p(b.get("scale")),
             _p(b.get("shift")), _p(b.get("mean")), _p(b.get("invstd")), int(b.get("relu", 0)),
             _p(b.get("p1")), _p(b.get("p2")), stream()), "conv2d_bwd_data")
 
 
 def wgrad_splits(G, B, H, W, Cin, Cout, R, stride, pad):
-    return lib.mauv_conv2d_wgrad_splits(G, B, H, W, Cin, Cout, R, R, stride, pad)
+    """Split-K slabs conv2d_bwd_weight writes for this problem (R: int or (R, S))."""
+    return _count(lib.mauv_conv2d_wgrad_splits(G, B, H, W, Cin, Cout, *_rs(R), stride, pad),
+                  "conv2d_wgrad_splits")
 
 
 def conv2d_bwd_weight(x, dy, ws, splits, G, B, H, W, Cin, Cout, R, stride, pad,
                       x_strides=None, x_bn=None, alg_cin=None):
-    """ws[splits][G][Cout][R*R*Cin] partial slabs (x' as in conv2d_fwd)."""
+    """ws[splits][G][Cout][R*S*Cin] partial slabs, columns in (r, s, c) order (x' and R as in
+    conv2d_fwd)."""
     xs = None if x_strides is None else _LL5(*x_strides)
     sc, sh, rl = x_bn if x_bn is not None else (None, None, 0)
-    Ho, Wo = out_hw(H, R, stride, pad), out_hw(W, R, stride, pad)
+    Rr, Ss = _rs(R)
+    Ho, Wo = out_hw(H, Rr, stride, pad), out_hw(W, Ss, stride, pad)
     xg = 1 if (x_strides is not None and x_strides[0] == 0) else G
-    fl = 2.0 * G * B * Ho * Wo * Cout * R * R * (alg_cin or Cin)
+    fl = 2.0 * G * B * Ho * Wo * Cout * Rr * Ss * (alg_cin or Cin)
     nb = dy.element_size() * (xg * B * H * W * Cin + G * B * Ho * Wo * Cout) + 4.0 * ws.numel()
     if dy.dtype in H16:
         _h16(dy.dtype, dy)
@@ -353,13 +381,13 @@ def conv2d_bwd_weight(x, dy, ws, splits, G, B, H, W, Cin, Cout, R, stride, pad,
                    info=(G, B, H, W, Cin, Cout, R, stride, pad, x_bn is not None)):
             check(lib.mauv_conv2d_bwd_weight_h16(H16[dy.dtype], _p(x), xs, _p(sc), _p(sh), int(rl),
                                                  _p(dy), _p(ws), splits, G, B, H, W, Cin, Cout,
-                                                 R, R, stride, pad, stream()),
+                                                 Rr, Ss, stride, pad, stream()),
                   "conv2d_bwd_weight_h16")
         return
     _f32(dy, ws)
     with _Prof("wgrad", fl, nb, info=(G, B, H, W, Cin, Cout, R, stride, pad, x_bn is not None)):
         check(lib.mauv_conv2d_bwd_weight_f32(_p(x), xs, _p(sc), _p(sh), int(rl), _p(dy), _p(ws),
-                                             splits, G, B, H, W, Cin, Cout, R, R, stride, pad,
+                                             splits, G, B, H, W, Cin, Cout, Rr, Ss, stride, pad,
                                              stream()), "conv2d_bwd_weight")
 
 
