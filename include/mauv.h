@@ -292,12 +292,22 @@ int mauv_adam_step(const MauvAdamEntry* table, int n, float lr, float beta1, flo
  * it, writes ok_loss (1 = the loss is finite on every rank) before the backward and counts
  * the gradient arena's non-finite elements into `nonfinite` after it.  mode / step_size /
  * bc2_sqrt are written by mauv_adam_step_gated; step is the Adam step count (bias correction);
- * poisoned = the arena still holds a skipped step's non-finite gradients. */
+ * poisoned = the arena still holds a skipped step's non-finite gradients.
+ * Global-norm gradient clipping: the caller writes max_norm (> 0 turns it on; 0, as in a
+ * zero-initialised gate, is off and the step is what it was without these words) and norm_kind
+ * (0 = L2, 1 = max-abs), and scans the gradients with mauv_grad_norm(..., &gate->grad_norm,
+ * &gate->nonfinite, ...) in place of mauv_nonfinite_count.  The library reads max_norm and
+ * grad_norm and writes clip_coef on every decision: min(1, max_norm / (grad_norm + 1e-6)) when
+ * max_norm > 0, else 1.  A gated Adam step multiplies every gradient element by clip_coef as it
+ * loads it (before maximize's negation and the weight-decay term, rounded on its own: the result
+ * of clipping in place and then stepping); the clipped gradient is never written back. */
 typedef struct MauvStepGate {
   int ok_loss, nonfinite, poisoned, mode;
   int step, stepped, skipped_loss, skipped_grad;
   float step_size, bc2_sqrt;
-  int reserved[6];   /* untouched by the library (mauv.train counts non-finite inputs in [5]) */
+  float max_norm, grad_norm, clip_coef;
+  int norm_kind;
+  int reserved[2];   /* untouched by the library (mauv.train counts non-finite inputs in [1]) */
 } MauvStepGate;
 int mauv_adam_step_gated(const MauvAdamEntry* table, int n, float lr, float beta1, float beta2,
                          float eps, float weight_decay, MauvStepGate* gate, hipStream_t stream);
@@ -332,6 +342,32 @@ typedef struct MauvAdamGroup {   /* 32 bytes */
 } MauvAdamGroup;
 int mauv_adam_step_ex(const MauvAdamEntryEx* table, int n, const MauvAdamGroup* groups,
                       int n_groups, long long step, MauvStepGate* gate, hipStream_t stream);
+
+/* ---- global gradient norm + non-finite scan, in-place clip (gradnorm.hip) -------------------
+ * torch.nn.utils.clip_grad_norm_ over a DEVICE table of fp32 spans: the flat gradient arena is
+ * one span, a plain parameter list one span per tensor; numel may be 0.  A span whose pointer is
+ * not 16-byte aligned takes scalar loads up to the first boundary.
+ * mauv_grad_norm: kind 0 = L2 (every square and the sum in double: no overflow or underflow for
+ * finite fp32 input), kind 1 = max-abs.  Blocks write double partials into `workspace`
+ * (mauv_grad_norm_workspace_bytes(n_spans) bytes, 8-byte aligned, no initialisation needed) and a
+ * one-block kernel joins them in a fixed order: no floating-point atomics, the same data gives
+ * the same bits.  *norm_out = the norm rounded once to fp32.  If any element was non-finite,
+ * *norm_out = NaN (both kinds) and a positive number is added to *nonfinite (may be NULL), which
+ * accumulates as with mauv_nonfinite_count.
+ * mauv_grad_clip: g *= (float)min(1.0, (double)max_norm / ((double)*norm + 1e-6)) over the same
+ * table, the coefficient formed on the device; nothing is written when it is 1 (also for a NaN
+ * norm: non-finite gradients are left as they are).
+ * Argument errors (n_spans outside 1..65535, a null table / workspace / norm, kind not 0 / 1,
+ * max_norm not finite or <= 0) return a negative code before any launch. */
+typedef struct MauvSpan {
+  const float* p;
+  long long numel;
+} MauvSpan;
+long long mauv_grad_norm_workspace_bytes(int n_spans);
+int mauv_grad_norm(const MauvSpan* spans, int n_spans, int kind, void* workspace, float* norm_out,
+                   int* nonfinite, hipStream_t stream);
+int mauv_grad_clip(const MauvSpan* spans, int n_spans, const float* norm, float max_norm,
+                   hipStream_t stream);
 
 /* ---- BatchNorm2d (training mode, per MC group) + residual + ReLU (bn.hip) ---------------
  * torchvision Bottleneck bn1..3 / downsample.1 / stem bn1 in .train() for every MC pass

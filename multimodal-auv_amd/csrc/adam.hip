@@ -10,6 +10,8 @@
 //   p -= lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
 // mauv_adam_step_ex is the same launch with torch's other options (amsgrad, maximize, decoupled
 // weight decay) and up to 8 parameter groups, each row naming its group.
+// The gated forms first multiply g by the gate's clip coefficient (global-norm gradient clipping,
+// DESIGN.md §2.36; 1 when it is off).
 #include "mauv_common.h"
 
 using namespace mauv;
@@ -35,11 +37,13 @@ __global__ __launch_bounds__(256) void adam_kernel(const MauvAdamEntry* __restri
                                                    float wd, float step_size, float bc2_sqrt,
                                                    const MauvStepGate* __restrict__ gate) {
   int mode = 1;
+  float clip = 1.0f;   // the gate's clip coefficient (1 when clipping is off: g * 1 is g)
   if (GATED) {
     mode = gate->mode;
     if (mode == 0) return;
     step_size = gate->step_size;
     bc2_sqrt = gate->bc2_sqrt;
+    clip = gate->clip_coef;
   }
   const MauvAdamEntry t = tab[blockIdx.y];
   float* grad = const_cast<float*>(t.grad);
@@ -60,7 +64,10 @@ __global__ __launch_bounds__(256) void adam_kernel(const MauvAdamEntry* __restri
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float pe = p[e], me = m[e], ve = v[e];
-        adam_elem(pe, g[e], me, ve, omb1, beta2, omb2, eps, wd, step_size, bc2_sqrt);
+        // the clipped gradient is rounded on its own (never contracted into g + wd * p), as
+        // if it had been clipped in place before the step
+        adam_elem(pe, GATED ? __fmul_rn(g[e], clip) : g[e], me, ve, omb1, beta2, omb2, eps, wd,
+                  step_size, bc2_sqrt);
         p[e] = pe; m[e] = me; v[e] = ve;
       }
       ((floatx4*)t.param)[i] = p;
@@ -75,7 +82,8 @@ __global__ __launch_bounds__(256) void adam_kernel(const MauvAdamEntry* __restri
        i += (long long)gridDim.x * 256) {
     if (upd) {
       float p = t.param[i], m = t.exp_avg[i], v = t.exp_avg_sq[i];
-      adam_elem(p, t.grad[i], m, v, omb1, beta2, omb2, eps, wd, step_size, bc2_sqrt);
+      adam_elem(p, GATED ? __fmul_rn(t.grad[i], clip) : t.grad[i], m, v, omb1, beta2, omb2, eps,
+                wd, step_size, bc2_sqrt);
       t.param[i] = p;
       t.exp_avg[i] = m;
       t.exp_avg_sq[i] = v;
@@ -89,7 +97,9 @@ __global__ __launch_bounds__(256) void adam_kernel(const MauvAdamEntry* __restri
 //                       (mode 2 zeroes it when it was clean before; a poisoned arena stays)
 //   grads non-finite -> no step, no zero_grad: the arena keeps them ("poisoned")
 //   otherwise        -> Adam at step count t+1, then zero_grad (mode 3)
-// and the non-finite counter is reset for the next scan.
+// and the non-finite counter is reset for the next scan.  Every decision also writes the clip
+// coefficient the Adam kernels multiply the gradient by: torch's clip_grad_norm_ formula over
+// the scan's grad_norm when max_norm > 0, else 1 (unused when the step is skipped).
 __global__ void step_gate_kernel(MauvStepGate* g, float lr, float beta1, float beta2) {
   const int ok_loss = g->ok_loss != 0, ok_grad = g->nonfinite == 0;
   if (ok_loss && ok_grad) {
@@ -114,6 +124,7 @@ __global__ void step_gate_kernel(MauvStepGate* g, float lr, float beta1, float b
     }
   }
   g->nonfinite = 0;
+  g->clip_coef = g->max_norm > 0.f ? clip_coef(g->max_norm, g->grad_norm) : 1.0f;
 }
 
 // ---- every option, several parameter groups (mauv_adam_step_ex) ------------------------------
@@ -127,13 +138,14 @@ struct AdamGroupsArg {
 };
 
 struct AdamConsts {
-  float omb1, beta2, omb2, eps, wd, decay, step_size, bc2_sqrt;
+  float omb1, beta2, omb2, eps, wd, decay, step_size, bc2_sqrt, clip;
 };
 
 // One element of torch's single-tensor Adam with the row's options; all off is adam_elem.
 template <bool AMS, bool MAXI, bool DEC>
 __device__ __forceinline__ void adam_elem_ex(float& p, float g, float& m, float& v, float& vmax,
                                              const AdamConsts& k) {
+  g = __fmul_rn(g, k.clip);   // first, where torch clips: .grad before step(); 1 when off
   if (!AMS && !MAXI && !DEC) {
     adam_elem(p, g, m, v, k.omb1, k.beta2, k.omb2, k.eps, k.wd, k.step_size, k.bc2_sqrt);
     return;
@@ -232,6 +244,7 @@ __global__ __launch_bounds__(256) void adam_ex_kernel(const MauvAdamEntryEx* __r
   k.decay = (float)(1.0 - (double)lr * (double)wd);
   k.step_size = ga.step_size[gi];
   k.bc2_sqrt = ga.bc2_sqrt[gi];
+  k.clip = GATED ? gate->clip_coef : 1.0f;
   if (GATED && (mode & 1)) {   // as step_gate_kernel forms them, at the gate's count
     const int st = gate->step;
     const double bc1 = 1.0 - pow((double)beta1, (double)st);

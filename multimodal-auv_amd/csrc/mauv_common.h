@@ -81,4 +81,11 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   return v;
 }
 
+// torch.nn.utils.clip_grad_norm_'s coefficient from the fp32 norm word: clamp(max_norm /
+// (norm + 1e-6), max = 1), formed in double and rounded once (step_gate_kernel, grad_clip_kernel).
+// A NaN norm (non-finite gradients) gives 1: fmin returns its other operand.
+__device__ __forceinline__ float clip_coef(float max_norm, float norm) {
+  return (float)fmin(1.0, (double)max_norm / ((double)norm + 1e-6));
+}
+
 }  // namespace mauv

@@ -54,6 +54,10 @@ SIGNATURES = {
     "mauv_adam_step": [P, I, F, F, F, F, F, LL, P],
     "mauv_adam_step_gated": [P, I, F, F, F, F, F, P, P],
     "mauv_adam_step_ex": [P, I, P, I, LL, P, P],
+    # gradnorm.hip
+    "mauv_grad_norm_workspace_bytes": [I],
+    "mauv_grad_norm": [P, I, I, P, P, P, P],
+    "mauv_grad_clip": [P, I, P, F, P],
     # bn.hip
     "mauv_bn_workspace_floats": [I, LL, I],
     "mauv_bn_fwd_train": [P, I, LL, I, P, P, P, P, F, F, P, P, P, P, P, P, I, P, P],
@@ -108,7 +112,8 @@ SIGNATURES = {
     "mauv_auroc_pairs": [P, P, I, P, P],
 }
 _RESTYPES = {"mauv_last_error": ctypes.c_char_p, "mauv_bn_workspace_floats": LL,
-             "mauv_bn_stats_workspace_floats": LL, "mauv_resize_workspace_bytes": LL}
+             "mauv_bn_stats_workspace_floats": LL, "mauv_resize_workspace_bytes": LL,
+             "mauv_grad_norm_workspace_bytes": LL}
 
 
 class MauvRoute(ctypes.Structure):

@@ -97,6 +97,7 @@ class GradArena:
             off += (p.numel() + self.ALIGN - 1) // self.ALIGN * self.ALIGN
         self.numel = off
         self.flat = torch.zeros(self.numel, device=device)
+        self.flat._mauv_gaps_zero = True   # (mauv.optim: the whole buffer scans as one span)
         self.views = [self.flat[o:o + p.numel()].view_as(p) for p, o in zip(self.params, offs)]
         self.offsets = offs
 

@@ -5,7 +5,9 @@
                                             for models on a ROCm device, torch's otherwise;
                                             optimizer_params[...] go in as keyword arguments,
                                             amsgrad / maximize / decoupled_weight_decay /
-                                            foreach / fused included, as into torch's Adam)
+                                            foreach / fused included, as into torch's Adam;
+                                            max_grad_norm / grad_norm_type turn global-norm
+                                            gradient clipping on for either optimizer)
 * ``train_and_evaluate_unimodal_model``     loop_utils.py:65-159 (epochs ``range(1, n)``)
 * ``train_and_evaluate_multimodal_model``   loop_utils.py:162-250 (scheduler stepped after
                                             training AND after evaluation, as the reference)
@@ -16,7 +18,7 @@ import os
 import torch.nn as nn
 import torch.optim as optim
 
-from .optim import FusedAdam
+from .optim import FusedAdam, check_max_grad_norm, check_grad_norm_type
 from .train import (train_unimodal_model, evaluate_unimodal_model, train_multimodal_model,
                     evaluate_multimodal_model)
 
@@ -31,8 +33,16 @@ def define_optimizers_and_schedulers(models_dict, optimizer_params=None, schedul
     criterion = nn.CrossEntropyLoss()
     def adam(model, kw):
         params = list(model.parameters())
-        on_gpu = all(p.is_cuda for p in params)
-        return (FusedAdam if on_gpu else optim.Adam)(params, **kw)
+        if all(p.is_cuda for p in params):
+            return FusedAdam(params, **kw)
+        # a host model: torch's Adam does not know the clipping options; they ride on the
+        # optimizer as attributes and mc_train_step clips with torch before its step()
+        kw = dict(kw)
+        clip = check_max_grad_norm(kw.pop("max_grad_norm", None))
+        kind = check_grad_norm_type(kw.pop("grad_norm_type", 2.0))
+        opt = optim.Adam(params, **kw)
+        opt.max_grad_norm, opt.grad_norm_type = clip, kind
+        return opt
     optimizers = {k: adam(models_dict[k], optimizer_params[k]) for k in _MODEL_KEYS}
     schedulers = {k: optim.lr_scheduler.StepLR(optimizers[k], **scheduler_params[k])
                   for k in optimizers}

@@ -796,3 +796,37 @@ def nonfinite_count(t, out):
     _dev(torch.float32, t)
     _dev(torch.int32, out)
     check(lib.mauv_nonfinite_count(_p(t), t.numel(), _p(out), stream()), "nonfinite_count")
+
+
+# ------------------------------------------------------------------ gradnorm.hip
+def grad_norm_workspace_bytes(n_spans):
+    n = int(lib.mauv_grad_norm_workspace_bytes(n_spans))
+    if n < 0:
+        check(n, "grad_norm_workspace_bytes")
+    return n
+
+
+def span_table(rows, device):
+    """Device MauvSpan table ([n, 2] int64: pointer, numel) of ``rows`` = [(data_ptr, numel)]."""
+    return torch.tensor(rows, dtype=torch.int64).reshape(-1, 2).to(device)
+
+
+def grad_norm(spans, kind, workspace, norm_out, nonfinite=None):
+    """*norm_out = the L2 (kind 0) or max-abs (kind 1) norm over a device span table, NaN when
+    an element is non-finite (then 1 is added to ``nonfinite`` as well); no host sync."""
+    _dev(torch.int64, spans)
+    _dev(torch.uint8, workspace)
+    _dev(torch.float32, norm_out)
+    _dev(torch.int32, nonfinite)
+    n = spans.shape[0]
+    if workspace.numel() < grad_norm_workspace_bytes(n):
+        raise ValueError("grad_norm: workspace smaller than grad_norm_workspace_bytes(n_spans)")
+    check(lib.mauv_grad_norm(_p(spans), n, kind, _p(workspace), _p(norm_out), _p(nonfinite),
+                             stream()), "grad_norm")
+
+
+def grad_clip(spans, norm, max_norm):
+    """g *= min(1, max_norm / (*norm + 1e-6)) over a device span table, in place."""
+    _dev(torch.int64, spans)
+    _dev(torch.float32, norm)
+    check(lib.mauv_grad_clip(_p(spans), spans.shape[0], _p(norm), max_norm, stream()), "grad_clip")

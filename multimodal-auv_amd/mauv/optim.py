@@ -23,8 +23,20 @@ multimodal.py:133-145 — skip on a non-finite loss, skip the step and the zero_
 non-finite gradients — is read from a device ``MauvStepGate`` by the kernel, and the Adam
 step count lives in that gate, so a training step never waits on the host.  It covers 1 to 8
 groups over the model's trainable parameters; frozen ones get no state and no step.
+
+``max_grad_norm`` (None, or a number > 0) with ``grad_norm_type`` (2 or inf) adds global-norm
+gradient clipping, ``torch.nn.utils.clip_grad_norm_(all parameters, max_grad_norm)`` ahead of the
+update, on the kernels of gradnorm.hip.  Both are plain attributes that may be reassigned between
+steps; they are no ``param_groups`` keys and stay out of ``state_dict()``.  ``step()`` scans the
+norm, clips in place and updates, without a host synchronisation.  The gated form scans with
+``scan_gated(gate)`` in place of the non-finite count, the gate forms the coefficient and the
+Adam kernel multiplies the gradient as it loads it: no extra pass.  ``last_grad_norm`` is the
+last step's pre-clip norm (torch's return value) as a 0-dim device tensor, NaN when a gradient
+was non-finite.  ``clip_grad_norm_`` below is the same clip as a function with torch's signature.
 """
 import ctypes
+import math
+import numbers
 
 import numpy as np
 import torch
@@ -34,6 +46,7 @@ from ._lib import lib, check, MauvAdamGroup
 
 GATE_WORDS = 16          # sizeof(MauvStepGate) / 4 (include/mauv.h)
 G_OK_LOSS, G_NONFINITE, G_POISONED, G_MODE, G_STEP, G_STEPPED, G_SKIP_LOSS, G_SKIP_GRAD = range(8)
+G_MAX_NORM, G_GRAD_NORM, G_CLIP_COEF, G_NORM_KIND = 10, 11, 12, 13   # fp32, fp32, fp32, int
 G_SCRATCH = 15           # a reserved word the training step counts non-finite inputs in
 MAX_GROUPS = 8           # MAUV_ADAM_MAX_GROUPS
 F_AMSGRAD, F_MAXIMIZE, F_DECOUPLED = 1, 2, 4
@@ -45,13 +58,77 @@ def _flags(group):
         (F_DECOUPLED if group["decoupled_weight_decay"] else 0)
 
 
+def check_max_grad_norm(v):
+    """``max_grad_norm``: None (no clipping) or a finite Python number > 0."""
+    if v is None:
+        return None
+    if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v) or v <= 0:
+        raise ValueError(f"max_grad_norm must be None or a finite number > 0, got {v!r}")
+    return float(v)
+
+
+def check_grad_norm_type(v):
+    """``grad_norm_type``: 2 (the L2 norm) or float("inf") (the largest magnitude)."""
+    if isinstance(v, bool) or not isinstance(v, numbers.Real) or v not in (2.0, math.inf):
+        raise ValueError(f"grad_norm_type must be 2 or float('inf'), got {v!r}")
+    return float(v)
+
+
+def _span_rows(grads):
+    """[(data_ptr, numel)] of a MauvSpan table over ``grads``: ONE row when they are exactly the
+    views of a gradient arena (mauv.engine.GradArena: views at 16-byte steps of one flat buffer
+    whose gaps stay zero, so they add nothing to either norm), else one row per tensor."""
+    base = grads[0]._base
+    if base is not None and getattr(base, "_mauv_gaps_zero", False):
+        end = base.data_ptr()
+        for g in sorted(grads, key=lambda g: g.data_ptr()):
+            if g._base is not base or g.data_ptr() != end:
+                break
+            end += (g.numel() + 3) // 4 * 16
+        else:
+            if end == base.data_ptr() + 4 * base.numel():
+                return [(base.data_ptr(), base.numel())]
+    return [(g.data_ptr(), g.numel()) for g in grads]
+
+
+class _NormPlan:
+    """The device span table and workspace of the norm scan / clip over one set of gradients,
+    rebuilt only when a pointer changes (like the Adam tables)."""
+
+    def __init__(self):
+        self.rows = self.spans = self.ws = None
+
+    def get(self, rows, device):
+        if self.rows != rows or self.spans.device != torch.device(device):
+            if len(rows) > 65535:
+                raise ValueError("gradient clipping: more than 65535 gradient tensors")
+            self.spans = ops.span_table(rows, device)
+            self.ws = torch.empty(ops.grad_norm_workspace_bytes(len(rows)), dtype=torch.uint8,
+                                  device=device)
+            self.rows = rows
+        return self.spans, self.ws
+
+
+def _kind(norm_type):
+    return 1 if norm_type == math.inf else 0
+
+
 class FusedAdam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
                  amsgrad=False, *, foreach=None, maximize=False, capturable=False,
-                 differentiable=False, fused=None, decoupled_weight_decay=False, **unsupported):
+                 differentiable=False, fused=None, decoupled_weight_decay=False,
+                 max_grad_norm=None, grad_norm_type=2.0, **unsupported):
         for k, v in unsupported.items():
             if v not in (None, False):
                 raise ValueError(f"FusedAdam: unsupported option {k}={v}")
+        # global-norm gradient clipping (torch.nn.utils.clip_grad_norm_ over every group's
+        # gradients before the update): plain attributes, not group keys and not in state_dict()
+        self.max_grad_norm = max_grad_norm
+        self.grad_norm_type = grad_norm_type
+        self.last_grad_norm = None   # 0-dim fp32 device tensor: the last step's pre-clip norm
+        self._norm_plan = _NormPlan()
+        self._norm_word = None
+        self._gate_clip = (0.0, 0)   # (max_norm, norm_kind) the device gate holds
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
                                       amsgrad=amsgrad, maximize=maximize, foreach=foreach,
                                       capturable=capturable, differentiable=differentiable,
@@ -68,6 +145,63 @@ class FusedAdam(torch.optim.Optimizer):
         self._gate_dirty = False   # the gate's step count is ahead of state["step"]
         self._gate_params = None
         self._gate_live = None     # [(parameter, group index)] the gate was built over
+
+    @property
+    def max_grad_norm(self):
+        return self.__dict__.get("_max_grad_norm")
+
+    @max_grad_norm.setter
+    def max_grad_norm(self, v):
+        self.__dict__["_max_grad_norm"] = check_max_grad_norm(v)
+
+    @property
+    def grad_norm_type(self):
+        return self.__dict__.get("_grad_norm_type", 2.0)
+
+    @grad_norm_type.setter
+    def grad_norm_type(self, v):
+        self.__dict__["_grad_norm_type"] = check_grad_norm_type(v)
+
+    def _clip_live(self):
+        """The ungated step's clip: norm scan over every group's live gradients, then the
+        in-place multiply — two launches of gradnorm.hip, no host synchronisation."""
+        grads = [p.grad for g in self.param_groups for p in g["params"] if p.grad is not None]
+        if not grads:
+            return
+        for g in grads:
+            if g.dtype != torch.float32 or not g.is_cuda or g.is_sparse or not g.is_contiguous():
+                raise TypeError("FusedAdam: dense contiguous fp32 ROCm gradients only")
+        dev = grads[0].device
+        spans, ws = self._norm_plan.get(_span_rows(grads), dev)
+        if self._norm_word is None or self._norm_word.device != dev:
+            self._norm_word = torch.zeros(1, device=dev)
+        ops.grad_norm(spans, _kind(self.grad_norm_type), ws, self._norm_word)
+        ops.grad_clip(spans, self._norm_word, self.max_grad_norm)
+        self.last_grad_norm = self._norm_word.clone()[0]
+
+    def _write_gate_clip(self, gate):
+        """The gate's max_norm / norm_kind words follow the attributes: a device fill when one
+        changed, no host synchronisation."""
+        want = (self.max_grad_norm or 0.0, _kind(self.grad_norm_type))
+        if self._gate_clip != want:
+            gate[G_MAX_NORM:G_MAX_NORM + 1].view(torch.float32).fill_(want[0])
+            gate[G_NORM_KIND:G_NORM_KIND + 1].fill_(want[1])
+            self._gate_clip = want
+
+    def scan_gated(self, gate, flat=None):
+        """With ``max_grad_norm`` set, the gated step's scan: the global norm of the gradients
+        into the gate's grad_norm word and their non-finite count into its nonfinite word, in
+        one pass (``flat``: the gradient arena every gradient is a view of — one span)."""
+        assert gate is self._gate, "scan_gated: use the gate returned by FusedAdam.gate()"
+        self._write_gate_clip(gate)
+        if flat is not None:
+            rows = [(flat.data_ptr(), flat.numel())]
+        else:
+            rows = _span_rows([p.grad for p, _ in self._gate_live])
+        spans, ws = self._norm_plan.get(rows, gate.device)
+        ops.grad_norm(spans, _kind(self.grad_norm_type), ws,
+                      gate[G_GRAD_NORM:G_GRAD_NORM + 1].view(torch.float32),
+                      gate[G_NONFINITE:G_NONFINITE + 1])
 
     @staticmethod
     def _check_group(group):
@@ -247,6 +381,10 @@ class FusedAdam(torch.optim.Optimizer):
                 loss = closure()
         self._sync_gate()
         self._gate = None   # an ungated step moves the count on the host: re-read it next time
+        if self.max_grad_norm is not None:
+            self._clip_live()
+        else:
+            self.last_grad_norm = None
         if not self._simple():
             self._step_ex()
             return loss
@@ -323,6 +461,7 @@ class FusedAdam(torch.optim.Optimizer):
             g[G_POISONED] = poisoned
             self._gate = g.to(device)
             self._gate_dirty = False
+            self._gate_clip = (0.0, 0)
         self._gate_params = params
         self._gate_live = pairs
         return self._gate
@@ -365,12 +504,15 @@ class FusedAdam(torch.optim.Optimizer):
         for hook in list(_topt._global_optimizer_pre_hooks.values()) + \
                 list(self._optimizer_step_pre_hooks.values()):
             hook(self, (self,), {})
+        self._write_gate_clip(gate)   # (the caller's scan_gated wrote them already when on)
         if simple:
             check(lib.mauv_adam_step_gated(tab.data_ptr(), len(live), group["lr"], b1, b2,
                                            group["eps"], group["weight_decay"], gate.data_ptr(),
                                            ops.stream()), "adam_step_gated")
         else:
             self._launch_ex(tab, 0, gate.data_ptr())
+        self.last_grad_norm = None if self.max_grad_norm is None else \
+            gate[G_GRAD_NORM:G_GRAD_NORM + 1].view(torch.float32).clone()[0]
         self._gate_dirty = True
         # what torch.optim.Optimizer.step's wrapper records: an LR scheduler stepped after this
         # does not warn "lr_scheduler.step() before optimizer.step()"; step hooks still run
@@ -427,3 +569,49 @@ class FusedAdamW(FusedAdam):
             raise ValueError("FusedAdamW: decoupled_weight_decay is always on")
         super().__init__(params, lr, betas, eps, weight_decay, amsgrad,
                          decoupled_weight_decay=True, **options)
+
+
+_clip_plans = {}   # (device, span rows) -> _NormPlan of clip_grad_norm_ (a few, oldest dropped)
+
+
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False, foreach=None):
+    """``torch.nn.utils.clip_grad_norm_`` (same arguments; a model stands for its parameters)
+    on gradnorm.hip: one scan and one in-place multiply over all gradients, returning the total
+    pre-clip norm as a 0-dim device tensor.  Nothing synchronises with the host — once the span
+    table of these gradient tensors is cached — unless ``error_if_nonfinite`` asks for the
+    check.  Non-finite gradients give a NaN norm and are left as they are.  Anything but dense
+    contiguous fp32 ROCm gradients on one device with norm_type 2 / inf and a finite
+    max_norm > 0 is handed to torch's function."""
+    if isinstance(parameters, torch.nn.Module):
+        parameters = list(parameters.parameters())
+    elif isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    else:
+        parameters = list(parameters)
+    grads = [p.grad for p in parameters if p.grad is not None]
+    try:
+        max_norm_f, kind = check_max_grad_norm(max_norm), _kind(check_grad_norm_type(norm_type))
+    except ValueError:
+        max_norm_f = None
+    if max_norm_f is None or not grads or len(grads) > 65535 or any(
+            g.dtype != torch.float32 or not g.is_cuda or g.is_sparse or not g.is_contiguous()
+            or g.device != grads[0].device for g in grads):
+        return torch.nn.utils.clip_grad_norm_(parameters, max_norm, norm_type,
+                                              error_if_nonfinite, foreach)
+    dev = grads[0].device
+    rows = _span_rows(grads)
+    key = (dev, tuple(rows))
+    plan = _clip_plans.get(key)
+    if plan is None:
+        while len(_clip_plans) >= 4:
+            _clip_plans.pop(next(iter(_clip_plans)))
+        plan = _clip_plans[key] = _NormPlan()
+    with torch.cuda.device(dev):
+        spans, ws = plan.get(rows, dev)
+        norm = torch.empty(1, device=dev)
+        ops.grad_norm(spans, kind, ws, norm)
+        if error_if_nonfinite and not bool(torch.isfinite(norm).item()):
+            raise RuntimeError(f"The total norm of order {norm_type} for gradients from "
+                               "`parameters` is non-finite, so it cannot be clipped.")
+        ops.grad_clip(spans, norm, max_norm_f)
+    return norm[0]

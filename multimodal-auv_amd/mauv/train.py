@@ -187,6 +187,28 @@ def _count_nonfinite(model, counter):
     ops.nonfinite_count(st.arena.flat, counter)
 
 
+def _scan_grad_norm(model, optimizer, gate):
+    """The clipped gated step's scan (FusedAdam.max_grad_norm set): the global gradient norm
+    into the gate and the arena's non-finite count beside it, in one pass over the same bytes
+    ``_count_nonfinite`` reads (gradnorm.hip; no host sync).  After ``allreduce_grads()`` the
+    arenas of all ranks are identical and the sum order is fixed, so every rank forms the same
+    coefficient without a further collective."""
+    st = unwrap(model).__dict__["_mauv_state"]
+    optimizer.scan_gated(gate, st.arena.flat)
+
+
+def _host_clip(optimizer):
+    """A torch optimizer built by define_optimizers_and_schedulers for a host model keeps the
+    clipping options as attributes: torch's own clip over its parameters ahead of step().
+    FusedAdam.step() clips by itself.  -> the pre-clip norm, or None."""
+    from .optim import FusedAdam
+    c = getattr(optimizer, "max_grad_norm", None)
+    if c is None or isinstance(optimizer, FusedAdam):
+        return None
+    params = [p for g in optimizer.param_groups for p in g["params"]]
+    return torch.nn.utils.clip_grad_norm_(params, c, getattr(optimizer, "grad_norm_type", 2.0))
+
+
 _MAX_STEPS_AHEAD = 2
 
 
@@ -214,7 +236,11 @@ def mc_train_step(model, inputs_tuple, labels, criterion, optimizer, num_mc, bat
     back out (non-finite loss: the reference never ran that backward), or leaves the arena
     alone (non-finite gradients: no zero_grad, multimodal.py:141-145).  Nothing here waits on
     the GPU; ``ok_loss`` / ``stepped`` come back as device tensors.  Other models and
-    optimizers take the host-decided path (None for a skipped batch)."""
+    optimizers take the host-decided path (None for a skipped batch).
+
+    With ``FusedAdam(max_grad_norm=...)`` the gated step clips the global gradient norm at no
+    extra pass: the norm rides on the non-finite scan, the gate forms the coefficient and the
+    Adam kernel multiplies as it loads the gradient; the result gains ``grad_norm`` (device)."""
     inflight = _throttle(model)
     loss, output, predicted, ce, scaled_kl = mc_loss(model, inputs_tuple, labels, criterion,
                                                      num_mc, batch_size, kl_w)
@@ -228,16 +254,22 @@ def mc_train_step(model, inputs_tuple, labels, criterion, optimizer, num_mc, bat
         loss.backward()
         if hasattr(model, "allreduce_grads"):  # mauv.ddp.DistributedMC: RCCL all-reduce
             model.allreduce_grads()
-        _count_nonfinite(model, gate[G_NONFINITE:G_NONFINITE + 1])
+        if optimizer.max_grad_norm is not None:
+            _scan_grad_norm(model, optimizer, gate)
+        else:
+            _count_nonfinite(model, gate[G_NONFINITE:G_NONFINITE + 1])
         optimizer.step_gated(gate)
         flags = gate[:G_STEPPED + 1].clone() != 0   # this batch's decisions (device)
         if inflight is not None:
             ev = torch.cuda.Event()
             ev.record()
             inflight.append(ev)
-        return dict(loss=loss.detach(), output=output, predicted=predicted, ce=ce.detach(),
-                    scaled_kl=scaled_kl.detach(), ok_loss=flags[G_OK_LOSS],
-                    stepped=flags[G_STEPPED])
+        r = dict(loss=loss.detach(), output=output, predicted=predicted, ce=ce.detach(),
+                 scaled_kl=scaled_kl.detach(), ok_loss=flags[G_OK_LOSS],
+                 stepped=flags[G_STEPPED])
+        if optimizer.last_grad_norm is not None:
+            r["grad_norm"] = optimizer.last_grad_norm
+        return r
     if not _all_ranks(model, bool(_batch_finite(loss, inputs_tuple).item())):
         logging.warning(f"Skipping batch due to NaN/Inf loss: {loss}")
         return None
@@ -245,13 +277,20 @@ def mc_train_step(model, inputs_tuple, labels, criterion, optimizer, num_mc, bat
     if hasattr(model, "allreduce_grads"):  # mauv.ddp.DistributedMC: one RCCL all-reduce
         model.allreduce_grads()
     stepped = _grads_finite(model)   # identical on every rank after the all-reduce
+    grad_norm = None
     if stepped:
+        grad_norm = _host_clip(optimizer)
         optimizer.step()
+        if grad_norm is None:   # FusedAdam with the option: the norm its own clip measured
+            grad_norm = getattr(optimizer, "last_grad_norm", None)
         optimizer.zero_grad()
     else:
         logging.warning("Skipping optimizer step due to NaN/Inf gradients")
-    return dict(loss=loss.detach(), output=output, predicted=predicted, ce=ce.detach(),
-                scaled_kl=scaled_kl.detach(), stepped=stepped)
+    r = dict(loss=loss.detach(), output=output, predicted=predicted, ce=ce.detach(),
+             scaled_kl=scaled_kl.detach(), stepped=stepped)
+    if grad_norm is not None:
+        r["grad_norm"] = grad_norm
+    return r
 
 
 class _TrainEpoch:
@@ -269,7 +308,7 @@ class _TrainEpoch:
         self.pending = []
 
     def add(self, i, r, labels):
-        keep = ("loss", "ce", "scaled_kl", "ok_loss", "stepped")
+        keep = ("loss", "ce", "scaled_kl", "ok_loss", "stepped", "grad_norm")
         r = dict({k: r[k] for k in keep if k in r},
                  n_correct=(r["predicted"] == labels).sum(), n=labels.size(0))
         self.pending.append((i, r))
@@ -293,6 +332,8 @@ class _TrainEpoch:
         self.total += r["n"]
         self.last = r
         self.writer.add_scalar("Loss/train", lv, i)
+        if "grad_norm" in r:   # gradient clipping on: the pre-clip norm, NaN for a skipped step
+            self.writer.add_scalar("GradNorm/train", float(r["grad_norm"]), i)
         logging.info(f"[Epoch {self.epoch} | Batch {i}] Loss: {lv:.4f}, "
                      f"Accuracy: {self.correct / max(self.total, 1):.4f}")
 
@@ -584,6 +625,7 @@ def train_unimodal_model(model, dataloader, criterion, optimizer, epoch, total_n
                     predicted = output.detach().float().max(1)[1]
                 loss = ce + kl_w * (kl / dataloader.batch_size)
                 loss.backward()
+                _host_clip(optimizer)
                 optimizer.step()
                 lv = loss.item()
                 total_loss += lv
