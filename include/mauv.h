@@ -342,6 +342,37 @@ typedef struct MauvAdamGroup {   /* 32 bytes */
 } MauvAdamGroup;
 int mauv_adam_step_ex(const MauvAdamEntryEx* table, int n, const MauvAdamGroup* groups,
                       int n_groups, long long step, MauvStepGate* gate, hipStream_t stream);
+/* Dynamic loss scaling (torch.amp.GradScaler's algorithm) decided and applied on the device.
+ * 32-byte device struct beside the gate; the caller initialises it (scale > 0, growth_factor,
+ * backoff_factor, growth_interval; the rest 0) and runs the backward on loss * scale, so the
+ * gradients the scan and the step see are `scale` times the true ones.  growth_interval == 0 is
+ * a static scale: the library never changes `scale`.  The library writes unscale, the counters
+ * and, when dynamic, scale and growth_tracker.  overflows counts the steps skipped on non-finite
+ * scaled gradients, growths the times growth_tracker reached growth_interval.  The factors are
+ * fp32: a scale update is (float)((double)scale * (double)factor), torch's rounding. */
+typedef struct MauvLossScale {
+  float scale, unscale, growth_factor, backoff_factor;
+  int growth_interval, growth_tracker, overflows, growths;
+} MauvLossScale;
+/* The gated mauv_adam_step_ex with a loss scaler.  scaler == NULL: exactly
+ * mauv_adam_step_ex(table, n, groups, n_groups, 0, gate, stream).  Otherwise one thread decides,
+ * unscale = (float)(1.0 / (double)scale) being formed first, from the scale the backward used:
+ *   ok_loss == 0   -> as without a scaler (mode 2, or 0 on a poisoned arena); scaler untouched
+ *   nonfinite != 0 -> no step and the gradients are ZEROED (mode 2; poisoned = 0, stepped = 0,
+ *                     skipped_grad += 1), overflows += 1; dynamic: scale *= backoff_factor,
+ *                     growth_tracker = 0
+ *   otherwise      -> Adam at step + 1, gradients zeroed (mode 3); dynamic: growth_tracker += 1,
+ *                     and on reaching growth_interval scale *= growth_factor if the product is
+ *                     finite, growth_tracker = 0, growths += 1
+ * With max_norm > 0 the scanned grad_norm (of the scaled gradients) is rewritten as
+ * grad_norm * unscale, the true norm (NaN stays NaN), and clip_coef is formed from that.  The
+ * Adam kernel loads each gradient as fl32(fl32(g * unscale) * clip_coef): two roundings in
+ * torch's order (GradScaler.unscale_, then clip_grad_norm_), never contracted into the
+ * weight-decay term and never written back.  Argument errors (a null table / groups / gate,
+ * n outside 1..65535, n_groups outside 1..8) return a negative code before any launch. */
+int mauv_adam_step_ex_scaled(const MauvAdamEntryEx* table, int n, const MauvAdamGroup* groups,
+                             int n_groups, MauvStepGate* gate, MauvLossScale* scaler,
+                             hipStream_t stream);
 
 /* ---- global gradient norm + non-finite scan, in-place clip (gradnorm.hip) -------------------
  * torch.nn.utils.clip_grad_norm_ over a DEVICE table of fp32 spans: the flat gradient arena is

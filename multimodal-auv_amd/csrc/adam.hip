@@ -11,7 +11,9 @@
 // mauv_adam_step_ex is the same launch with torch's other options (amsgrad, maximize, decoupled
 // weight decay) and up to 8 parameter groups, each row naming its group.
 // The gated forms first multiply g by the gate's clip coefficient (global-norm gradient clipping,
-// DESIGN.md §2.36; 1 when it is off).
+// DESIGN.md §2.36; 1 when it is off).  mauv_adam_step_ex_scaled is the gated launch with dynamic
+// loss scaling (torch.amp.GradScaler's algorithm): the decision also backs the
+// scale off or grows it, and the kernel multiplies g by 1 / scale ahead of the clip coefficient.
 #include "mauv_common.h"
 
 using namespace mauv;
@@ -92,6 +94,21 @@ __global__ __launch_bounds__(256) void adam_kernel(const MauvAdamEntry* __restri
   }
 }
 
+// The "otherwise" branch of both decisions below: the bias-correction constants at the next
+// step count, Adam + zero_grad.
+__device__ __forceinline__ void gate_take_step(MauvStepGate* g, float lr, float beta1,
+                                               float beta2) {
+  const int t = g->step + 1;
+  const double bc1 = 1.0 - pow((double)beta1, (double)t);
+  const double bc2 = 1.0 - pow((double)beta2, (double)t);
+  g->step = t;
+  g->step_size = (float)((double)lr / bc1);
+  g->bc2_sqrt = (float)sqrt(bc2);
+  g->mode = 3;
+  g->poisoned = 0;
+  g->stepped = 1;
+}
+
 // The step decision of train/multimodal.py:133-145 taken on the device (one thread):
 //   loss non-finite  -> no step; the batch's gradients are taken back out of the arena
 //                       (mode 2 zeroes it when it was clean before; a poisoned arena stays)
@@ -103,15 +120,7 @@ __global__ __launch_bounds__(256) void adam_kernel(const MauvAdamEntry* __restri
 __global__ void step_gate_kernel(MauvStepGate* g, float lr, float beta1, float beta2) {
   const int ok_loss = g->ok_loss != 0, ok_grad = g->nonfinite == 0;
   if (ok_loss && ok_grad) {
-    const int t = g->step + 1;
-    const double bc1 = 1.0 - pow((double)beta1, (double)t);
-    const double bc2 = 1.0 - pow((double)beta2, (double)t);
-    g->step = t;
-    g->step_size = (float)((double)lr / bc1);
-    g->bc2_sqrt = (float)sqrt(bc2);
-    g->mode = 3;
-    g->poisoned = 0;
-    g->stepped = 1;
+    gate_take_step(g, lr, beta1, beta2);
   } else {
     g->stepped = 0;
     if (!ok_loss) {
@@ -127,6 +136,62 @@ __global__ void step_gate_kernel(MauvStepGate* g, float lr, float beta1, float b
   g->clip_coef = g->max_norm > 0.f ? clip_coef(g->max_norm, g->grad_norm) : 1.0f;
 }
 
+// The same decision with a loss scaler beside the gate (one thread).  The
+// arena holds the gradients of loss * scale:
+//   loss non-finite  -> as above; the scaler is not touched (a NaN input is no overflow)
+//   grads non-finite -> an overflow of the scaled gradients: no step, the arena is zeroed
+//                       (mode 2; never "poisoned": the next batch starts clean, as GradScaler
+//                       followed by zero_grad), scale *= backoff_factor, growth_tracker = 0
+//   otherwise        -> Adam + zero_grad as above; growth_tracker += 1, and when it reaches
+//                       growth_interval: scale *= growth_factor if that is finite (torch's
+//                       _amp_update_scale_), growth_tracker = 0
+// growth_interval == 0 is a static scale: only the counters move.  unscale = 1 / scale is formed
+// from the scale the backward ran with, before it changes; the scanned norm is the scaled
+// gradients', so grad_norm is rewritten as the true norm before the clip coefficient is formed.
+__global__ void step_gate_scaled_kernel(MauvStepGate* g, MauvLossScale* s, float lr, float beta1,
+                                        float beta2) {
+  const int ok_loss = g->ok_loss != 0, ok_grad = g->nonfinite == 0;
+  const float scale = s->scale;
+  const float unscale = (float)(1.0 / (double)scale);
+  const bool dynamic = s->growth_interval != 0;
+  s->unscale = unscale;
+  if (!ok_loss) {
+    g->stepped = 0;
+    g->mode = g->poisoned ? 0 : 2;
+    g->skipped_loss += 1;
+  } else if (!ok_grad) {
+    g->stepped = 0;
+    g->mode = 2;
+    g->poisoned = 0;
+    g->skipped_grad += 1;
+    s->overflows += 1;
+    if (dynamic) {
+      s->scale = (float)((double)scale * (double)s->backoff_factor);   // torch's rounding
+      s->growth_tracker = 0;
+    }
+  } else {
+    gate_take_step(g, lr, beta1, beta2);
+    if (dynamic) {
+      const int ok_steps = s->growth_tracker + 1;
+      if (ok_steps == s->growth_interval) {
+        const float grown = (float)((double)scale * (double)s->growth_factor);
+        if (isfinite(grown)) s->scale = grown;
+        s->growth_tracker = 0;
+        s->growths += 1;
+      } else {
+        s->growth_tracker = ok_steps;
+      }
+    }
+  }
+  g->nonfinite = 0;
+  if (g->max_norm > 0.f) {
+    g->grad_norm = __fmul_rn(g->grad_norm, unscale);   // (a NaN stays NaN)
+    g->clip_coef = clip_coef(g->max_norm, g->grad_norm);
+  } else {
+    g->clip_coef = 1.0f;
+  }
+}
+
 // ---- every option, several parameter groups (mauv_adam_step_ex) ------------------------------
 // The groups travel by value in the kernel arguments (a StepLR-changed lr needs no device copy);
 // step_size / bc2_sqrt are the host's for the ungated step, formed per block from the gate's
@@ -138,14 +203,16 @@ struct AdamGroupsArg {
 };
 
 struct AdamConsts {
-  float omb1, beta2, omb2, eps, wd, decay, step_size, bc2_sqrt, clip;
+  float omb1, beta2, omb2, eps, wd, decay, step_size, bc2_sqrt, clip, unscale;
 };
 
 // One element of torch's single-tensor Adam with the row's options; all off is adam_elem.
 template <bool AMS, bool MAXI, bool DEC>
 __device__ __forceinline__ void adam_elem_ex(float& p, float g, float& m, float& v, float& vmax,
                                              const AdamConsts& k) {
-  g = __fmul_rn(g, k.clip);   // first, where torch clips: .grad before step(); 1 when off
+  // first, where torch's GradScaler.unscale_ and then clip_grad_norm_ work: on .grad before
+  // step(), each product rounded on its own; both factors are 1 when off (g * 1 is g)
+  g = __fmul_rn(__fmul_rn(g, k.unscale), k.clip);
   if (!AMS && !MAXI && !DEC) {
     adam_elem(p, g, m, v, k.omb1, k.beta2, k.omb2, k.eps, k.wd, k.step_size, k.bc2_sqrt);
     return;
@@ -214,7 +281,8 @@ __device__ __forceinline__ void adam_row(const MauvAdamEntryEx& t, long long n4,
 template <bool GATED>
 __global__ __launch_bounds__(256) void adam_ex_kernel(const MauvAdamEntryEx* __restrict__ tab,
                                                       AdamGroupsArg ga, int n_groups,
-                                                      const MauvStepGate* __restrict__ gate) {
+                                                      const MauvStepGate* __restrict__ gate,
+                                                      const MauvLossScale* __restrict__ ls) {
   int mode = 1;
   if (GATED) {
     mode = gate->mode;
@@ -245,6 +313,7 @@ __global__ __launch_bounds__(256) void adam_ex_kernel(const MauvAdamEntryEx* __r
   k.step_size = ga.step_size[gi];
   k.bc2_sqrt = ga.bc2_sqrt[gi];
   k.clip = GATED ? gate->clip_coef : 1.0f;
+  k.unscale = (GATED && ls) ? ls->unscale : 1.0f;   // written by step_gate_scaled_kernel
   if (GATED && (mode & 1)) {   // as step_gate_kernel forms them, at the gate's count
     const int st = gate->step;
     const double bc1 = 1.0 - pow((double)beta1, (double)st);
@@ -321,10 +390,40 @@ MAUV_API int mauv_adam_step_ex(const MauvAdamEntryEx* table, int n, const MauvAd
     hipLaunchKernelGGL(step_gate_kernel, dim3(1), dim3(1), 0, stream, gate, groups[0].lr,
                        groups[0].beta1, groups[0].beta2);
     hipLaunchKernelGGL(adam_ex_kernel<true>, dim3(64, n), dim3(256), 0, stream, table, ga,
-                       n_groups, (const MauvStepGate*)gate);
+                       n_groups, (const MauvStepGate*)gate, nullptr);
   } else {
     hipLaunchKernelGGL(adam_ex_kernel<false>, dim3(64, n), dim3(256), 0, stream, table, ga,
-                       n_groups, nullptr);
+                       n_groups, nullptr, nullptr);
   }
   return check_launch("adam_step_ex");
+}
+
+// The gated mauv_adam_step_ex with a loss scaler (mauv.h): the scaled decision, then the same
+// Adam launch reading 1 / scale beside the clip coefficient.  scaler == NULL is exactly
+// mauv_adam_step_ex(table, n, groups, n_groups, 0, gate, stream).
+MAUV_API int mauv_adam_step_ex_scaled(const MauvAdamEntryEx* table, int n,
+                                      const MauvAdamGroup* groups, int n_groups,
+                                      MauvStepGate* gate, MauvLossScale* scaler,
+                                      hipStream_t stream) {
+  if (n <= 0 || n > 65535 || !table) {
+    set_error("adam_step_ex_scaled: bad table size");
+    return kErrArg;
+  }
+  if (n_groups < 1 || n_groups > MAUV_ADAM_MAX_GROUPS || !groups) {
+    set_error("adam_step_ex_scaled: 1..8 parameter groups");
+    return kErrArg;
+  }
+  if (!gate) { set_error("adam_step_ex_scaled: no gate"); return kErrArg; }
+  if (!scaler) return mauv_adam_step_ex(table, n, groups, n_groups, 0, gate, stream);
+  AdamGroupsArg ga = {};
+  for (int i = 0; i < n_groups; ++i) {
+    ga.g[i] = groups[i];
+    ga.step_size[i] = 0.f;
+    ga.bc2_sqrt[i] = 1.f;
+  }
+  hipLaunchKernelGGL(step_gate_scaled_kernel, dim3(1), dim3(1), 0, stream, gate, scaler,
+                     groups[0].lr, groups[0].beta1, groups[0].beta2);
+  hipLaunchKernelGGL(adam_ex_kernel<true>, dim3(64, n), dim3(256), 0, stream, table, ga,
+                     n_groups, (const MauvStepGate*)gate, (const MauvLossScale*)scaler);
+  return check_launch("adam_step_ex_scaled");
 }

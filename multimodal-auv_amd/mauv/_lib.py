@@ -54,6 +54,7 @@ SIGNATURES = {
     "mauv_adam_step": [P, I, F, F, F, F, F, LL, P],
     "mauv_adam_step_gated": [P, I, F, F, F, F, F, P, P],
     "mauv_adam_step_ex": [P, I, P, I, LL, P, P],
+    "mauv_adam_step_ex_scaled": [P, I, P, I, P, P, P],
     # gradnorm.hip
     "mauv_grad_norm_workspace_bytes": [I],
     "mauv_grad_norm": [P, I, I, P, P, P, P],
@@ -127,6 +128,12 @@ class MauvAdamGroup(ctypes.Structure):
     """include/mauv.h MauvAdamGroup: one parameter group of mauv_adam_step_ex (32 bytes)."""
     _fields_ = [("lr", F), ("beta1", F), ("beta2", F), ("eps", F), ("weight_decay", F),
                 ("flags", U32), ("reserved", I * 2)]
+
+
+class MauvLossScale(ctypes.Structure):
+    """include/mauv.h MauvLossScale: the device loss-scaler state (32 bytes)."""
+    _fields_ = [("scale", F), ("unscale", F), ("growth_factor", F), ("backoff_factor", F),
+                ("growth_interval", I), ("growth_tracker", I), ("overflows", I), ("growths", I)]
 
 
 class MauvError(RuntimeError):

@@ -33,6 +33,21 @@ norm, clips in place and updates, without a host synchronisation.  The gated for
 Adam kernel multiplies the gradient as it loads it: no extra pass.  ``last_grad_norm`` is the
 last step's pre-clip norm (torch's return value) as a 0-dim device tensor, NaN when a gradient
 was non-finite.  ``clip_grad_norm_`` below is the same clip as a function with torch's signature.
+
+``loss_scale`` (None, ``"dynamic"``, a number for a static scale, or a ``mauv.amp.LossScaler``)
+adds dynamic loss scaling, ``torch.amp.GradScaler``'s algorithm, for f16 training (DESIGN.md
+§2.37).  It is a plain attribute like ``max_grad_norm``: no ``param_groups`` key, not in
+``state_dict()`` (the scaler has its own).  The caller runs the backward on
+``opt.loss_scale.scale(loss)`` (mauv.train does).  The gated form then hands the scaler's device
+state to ``mauv_adam_step_ex_scaled``: the decision skips the step and zeroes the gradients on an
+overflow, backs the scale off or grows it, and the kernel multiplies each gradient by 1 / scale
+ahead of the clip coefficient; ``last_grad_norm`` is the norm of the unscaled gradients.
+``step()`` with a scaler set goes through the same device decision on a gate of its own over the
+live parameters (``ok_loss`` = 1): it scans, unscales, clips, steps AND zeroes the gradients
+(stepped or skipped, as GradScaler's ``step`` followed by ``zero_grad``), a skipped step does not
+advance Adam's step count, and nothing waits on the host.  Where the gated form cannot apply —
+parameters with different step counts, more than 8 groups — it raises a ValueError rather than
+step on scaled gradients.
 """
 import ctypes
 import math
@@ -43,6 +58,7 @@ import torch
 
 from . import ops  # noqa: F401  (loads the library)
 from ._lib import lib, check, MauvAdamGroup
+from .amp import as_loss_scaler
 
 GATE_WORDS = 16          # sizeof(MauvStepGate) / 4 (include/mauv.h)
 G_OK_LOSS, G_NONFINITE, G_POISONED, G_MODE, G_STEP, G_STEPPED, G_SKIP_LOSS, G_SKIP_GRAD = range(8)
@@ -117,7 +133,7 @@ class FusedAdam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
                  amsgrad=False, *, foreach=None, maximize=False, capturable=False,
                  differentiable=False, fused=None, decoupled_weight_decay=False,
-                 max_grad_norm=None, grad_norm_type=2.0, **unsupported):
+                 max_grad_norm=None, grad_norm_type=2.0, loss_scale=None, **unsupported):
         for k, v in unsupported.items():
             if v not in (None, False):
                 raise ValueError(f"FusedAdam: unsupported option {k}={v}")
@@ -129,6 +145,8 @@ class FusedAdam(torch.optim.Optimizer):
         self._norm_plan = _NormPlan()
         self._norm_word = None
         self._gate_clip = (0.0, 0)   # (max_norm, norm_kind) the device gate holds
+        # dynamic loss scaling (mauv.amp.LossScaler): a plain attribute too
+        self.loss_scale = loss_scale
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
                                       amsgrad=amsgrad, maximize=maximize, foreach=foreach,
                                       capturable=capturable, differentiable=differentiable,
@@ -161,6 +179,20 @@ class FusedAdam(torch.optim.Optimizer):
     @grad_norm_type.setter
     def grad_norm_type(self, v):
         self.__dict__["_grad_norm_type"] = check_grad_norm_type(v)
+
+    @property
+    def loss_scale(self):
+        """The optimizer's ``mauv.amp.LossScaler``, or None."""
+        return self.__dict__.get("_loss_scale")
+
+    @loss_scale.setter
+    def loss_scale(self, v):
+        self.__dict__["_loss_scale"] = as_loss_scaler(v)
+
+    def _scaler(self):
+        """The loss scaler when it is set and enabled, else None."""
+        ls = self.loss_scale
+        return ls if ls is not None and ls.is_enabled() else None
 
     def _clip_live(self):
         """The ungated step's clip: norm scan over every group's live gradients, then the
@@ -280,16 +312,23 @@ class FusedAdam(torch.optim.Optimizer):
         self._tables[key] = (ident, tab)
         return tab
 
-    def _launch_ex(self, tab, t, gate):
+    def _launch_ex(self, tab, t, gate, scaler=None):
         """mauv_adam_step_ex over every launch of ``tab``; the groups' current lr, betas, eps,
-        weight_decay and flags travel by value."""
+        weight_decay and flags travel by value.  ``scaler``: the device MauvLossScale pointer of
+        a gated step with loss scaling (mauv_adam_step_ex_scaled; one launch)."""
         table, chunks = tab
+        assert scaler is None or (gate is not None and len(chunks) == 1)
         for r0, n, gis in chunks:
             arr = (MauvAdamGroup * len(gis))()
             for a, gi in zip(arr, gis):
                 g = self.param_groups[gi]
                 a.lr, a.eps, a.weight_decay = g["lr"], g["eps"], g["weight_decay"]
                 (a.beta1, a.beta2), a.flags = g["betas"], _flags(g)
+            if scaler is not None:
+                check(lib.mauv_adam_step_ex_scaled(table.data_ptr() + 56 * r0, n,
+                                                   ctypes.addressof(arr), len(gis), gate, scaler,
+                                                   ops.stream()), "adam_step_ex_scaled")
+                continue
             check(lib.mauv_adam_step_ex(table.data_ptr() + 56 * r0, n, ctypes.addressof(arr),
                                         len(gis), t, gate, ops.stream()), "adam_step_ex")
 
@@ -379,6 +418,9 @@ class FusedAdam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        if self._scaler() is not None:
+            self._step_scaled()
+            return loss
         self._sync_gate()
         self._gate = None   # an ungated step moves the count on the host: re-read it next time
         if self.max_grad_norm is not None:
@@ -419,6 +461,46 @@ class FusedAdam(torch.optim.Optimizer):
                 if len(steps) == 1:
                     self._remember(gi, ps, t, tab)
         return loss
+
+    def _step_scaled(self):
+        """``step()`` with a loss scaler: the gated step on a gate of this optimizer's own over
+        the live parameters, the loss taken as finite.  The scan (norm + non-finite count), the
+        decision and the Adam launch are queued; nothing is read back."""
+        if len(self.param_groups) > MAX_GROUPS:
+            raise ValueError(f"FusedAdam: loss scaling steps through the device-gated form, "
+                             f"which takes at most {MAX_GROUPS} parameter groups "
+                             f"({len(self.param_groups)} given)")
+        pairs = [(p, gi) for gi, g in enumerate(self.param_groups) for p in g["params"]
+                 if p.grad is not None]
+        if not pairs:
+            return
+        for p, _ in pairs:
+            g = p.grad
+            if g.dtype != torch.float32 or not g.is_cuda or g.is_sparse or not g.is_contiguous():
+                raise TypeError("FusedAdam: dense contiguous fp32 ROCm gradients only")
+        dev = pairs[0][0].device
+        same = self._gate is not None and self._gate.device == dev and \
+            self._gate_live is not None and len(self._gate_live) == len(pairs) and \
+            all(a is b and i == j for (a, i), (b, j) in zip(self._gate_live, pairs))
+        if not same:
+            self._sync_gate()
+            counts = {int(self.state[p]["step"].item()) if "step" in self.state.get(p, ()) else 0
+                      for p, _ in pairs}
+            if len(counts) != 1:
+                raise ValueError("FusedAdam: loss scaling steps through the device-gated form, "
+                                 "which needs one step count for all parameters "
+                                 f"(found {sorted(counts)})")
+            g = torch.zeros(GATE_WORDS, dtype=torch.int32)
+            g[G_STEP] = counts.pop()
+            self._gate = g.to(dev)
+            self._gate_dirty = False
+            self._gate_clip = (0.0, 0)
+            self._gate_params = None
+            self._gate_live = pairs
+        gate = self._gate
+        gate[G_OK_LOSS:G_OK_LOSS + 1].fill_(1)
+        self.scan_gated(gate)
+        self._step_gated(gate)
 
     # ---- the device-gated form ---------------------------------------------------------------
     def gate(self, params, device):
@@ -472,16 +554,34 @@ class FusedAdam(torch.optim.Optimizer):
         from ``gate`` — no host synchronisation.  Every trainable parameter of every group must
         hold a gradient (the model's arena views); frozen ones get no state and no step."""
         assert gate is self._gate, "step_gated: use the gate returned by FusedAdam.gate()"
+        from torch.optim import optimizer as _topt
+        for hook in list(_topt._global_optimizer_pre_hooks.values()) + \
+                list(self._optimizer_step_pre_hooks.values()):
+            hook(self, (self,), {})
+        self._step_gated(gate)
+        # what torch.optim.Optimizer.step's wrapper records: an LR scheduler stepped after this
+        # does not warn "lr_scheduler.step() before optimizer.step()"; step hooks still run
+        self._opt_called = True
+        for hook in list(self._optimizer_step_post_hooks.values()) + \
+                list(_topt._global_optimizer_post_hooks.values()):
+            hook(self, (self,), {})
+
+    def _step_gated(self, gate):
+        """step_gated without the step hooks (``step()`` runs them itself)."""
         pairs = self._gate_live
         live = [p for p, _ in pairs]
         if any(p.grad is None for p in live):
             raise RuntimeError("step_gated: every parameter needs a gradient tensor")
-        simple = self._simple()
+        ls = self._scaler()
+        # with a loss scaler every layout takes the all-groups entry: one plain group there is
+        # adam_elem, the simple kernel's element
+        simple = self._simple() and ls is None
         if simple:
             group = self.param_groups[0]
             b1, b2 = group["betas"]
             fast = self._fast_entry(0, live)
             if fast is None:
+                self._fast.pop(EX, None)   # (its step buffer is re-homed below)
                 self._prepare(0, group, live)
                 tab = self._table(0, live)
                 t = int(self._gate_step_host())
@@ -492,6 +592,7 @@ class FusedAdam(torch.optim.Optimizer):
             fast = self._fast_entry(EX, live)
             if fast is None or fast[7] != layout:
                 self._fast.pop(EX, None)
+                self._fast.pop(0, None)    # (its step buffer is re-homed below)
                 for gi, group in enumerate(self.param_groups):
                     self._prepare(EX, group, [p for p, g in pairs if g == gi])
                 tab = self._table_ex(EX, pairs)
@@ -500,26 +601,17 @@ class FusedAdam(torch.optim.Optimizer):
                 self._remember(EX, live, t, tab, layout)
                 fast = self._fast[EX]
         tab = fast[5]
-        from torch.optim import optimizer as _topt
-        for hook in list(_topt._global_optimizer_pre_hooks.values()) + \
-                list(self._optimizer_step_pre_hooks.values()):
-            hook(self, (self,), {})
         self._write_gate_clip(gate)   # (the caller's scan_gated wrote them already when on)
         if simple:
             check(lib.mauv_adam_step_gated(tab.data_ptr(), len(live), group["lr"], b1, b2,
                                            group["eps"], group["weight_decay"], gate.data_ptr(),
                                            ops.stream()), "adam_step_gated")
         else:
-            self._launch_ex(tab, 0, gate.data_ptr())
+            self._launch_ex(tab, 0, gate.data_ptr(),
+                            None if ls is None else ls.device_state(gate.device).data_ptr())
         self.last_grad_norm = None if self.max_grad_norm is None else \
             gate[G_GRAD_NORM:G_GRAD_NORM + 1].view(torch.float32).clone()[0]
         self._gate_dirty = True
-        # what torch.optim.Optimizer.step's wrapper records: an LR scheduler stepped after this
-        # does not warn "lr_scheduler.step() before optimizer.step()"; step hooks still run
-        self._opt_called = True
-        for hook in list(self._optimizer_step_post_hooks.values()) + \
-                list(_topt._global_optimizer_post_hooks.values()):
-            hook(self, (self,), {})
 
     def _gate_step_host(self):
         """Step count held by the gate (one device read; only on a cache rebuild)."""

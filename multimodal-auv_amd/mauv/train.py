@@ -209,6 +209,32 @@ def _host_clip(optimizer):
     return torch.nn.utils.clip_grad_norm_(params, c, getattr(optimizer, "grad_norm_type", 2.0))
 
 
+def _fused_scaler(optimizer):
+    """The enabled mauv.amp.LossScaler a FusedAdam carries (``loss_scale=``), else None."""
+    from .optim import FusedAdam
+    return optimizer._scaler() if isinstance(optimizer, FusedAdam) else None
+
+
+def _host_scaler(optimizer):
+    """The ``torch.amp.GradScaler("cpu")`` define_optimizers_and_schedulers hung on a torch
+    optimizer of a host model (``loss_scale=``), else None."""
+    from .optim import FusedAdam
+    return None if isinstance(optimizer, FusedAdam) else getattr(optimizer, "grad_scaler", None)
+
+
+def _scaled_step_host(model, optimizer, gs):
+    """The host model's step under a torch GradScaler, in torch's order: unscale_, the clip
+    over the unscaled gradients, step (skipped by the scaler on an overflow), update, and the
+    zero_grad that follows either way.  -> (stepped, pre-clip norm or None)."""
+    gs.unscale_(optimizer)
+    stepped = _grads_finite(model)        # the scaler's own found-inf decision
+    grad_norm = _host_clip(optimizer) if stepped else None
+    gs.step(optimizer)
+    gs.update()
+    optimizer.zero_grad()
+    return stepped, grad_norm
+
+
 _MAX_STEPS_AHEAD = 2
 
 
@@ -240,18 +266,32 @@ def mc_train_step(model, inputs_tuple, labels, criterion, optimizer, num_mc, bat
 
     With ``FusedAdam(max_grad_norm=...)`` the gated step clips the global gradient norm at no
     extra pass: the norm rides on the non-finite scan, the gate forms the coefficient and the
-    Adam kernel multiplies as it loads the gradient; the result gains ``grad_norm`` (device)."""
+    Adam kernel multiplies as it loads the gradient; the result gains ``grad_norm`` (device).
+
+    With ``FusedAdam(loss_scale=...)`` (mauv.amp.LossScaler; f16 trunks need it) the backward
+    runs on ``loss * scale``, the scale read on the device, and the same decision skips the step
+    on an overflow (the arena is zeroed, not kept), backs the scale off or grows it, while the
+    Adam kernel unscales as it loads; everything reported stays unscaled and the result gains
+    ``loss_scale``, the scale this batch ran with (device).  The host-decided path of the same
+    optimizer goes through the same device decision (``FusedAdam.step()``) and gives the same
+    bits.  A host model's torch optimizer carrying a ``torch.amp.GradScaler`` (``grad_scaler``,
+    hung there by define_optimizers_and_schedulers) is driven in torch's order.  DistributedMC:
+    the scan runs after ``allreduce_grads()``, so every rank sees the same arena, takes the same
+    decision and keeps the same scale; no collective is added."""
     inflight = _throttle(model)
     loss, output, predicted, ce, scaled_kl = mc_loss(model, inputs_tuple, labels, criterion,
                                                      num_mc, batch_size, kl_w)
     gate = _step_gate(model, optimizer, loss)
+    ls = _fused_scaler(optimizer) if loss.is_cuda else None
+    # the scale this batch's backward runs with (the step's decision may change it)
+    used_scale = None if ls is None else ls.scale_tensor(loss.device).clone()[0]
     if gate is not None:
         from .optim import G_OK_LOSS, G_NONFINITE, G_STEPPED, G_SCRATCH
         ok = gate[G_OK_LOSS:G_OK_LOSS + 1]
         ok.copy_(_batch_finite(loss, inputs_tuple, gate[G_SCRATCH:G_SCRATCH + 1]))
         if hasattr(model, "all_ranks_device"):
             model.all_ranks_device(ok)
-        loss.backward()
+        (loss if ls is None else loss * used_scale).backward()
         if hasattr(model, "allreduce_grads"):  # mauv.ddp.DistributedMC: RCCL all-reduce
             model.allreduce_grads()
         if optimizer.max_grad_norm is not None:
@@ -269,27 +309,51 @@ def mc_train_step(model, inputs_tuple, labels, criterion, optimizer, num_mc, bat
                  stepped=flags[G_STEPPED])
         if optimizer.last_grad_norm is not None:
             r["grad_norm"] = optimizer.last_grad_norm
+        if ls is not None:
+            r["loss_scale"] = used_scale
         return r
     if not _all_ranks(model, bool(_batch_finite(loss, inputs_tuple).item())):
         logging.warning(f"Skipping batch due to NaN/Inf loss: {loss}")
         return None
-    loss.backward()
+    gs = _host_scaler(optimizer)
+    if ls is not None:
+        (loss * used_scale).backward()
+    elif gs is not None:
+        used_scale = torch.tensor(gs.get_scale())
+        gs.scale(loss).backward()
+    else:
+        loss.backward()
     if hasattr(model, "allreduce_grads"):  # mauv.ddp.DistributedMC: one RCCL all-reduce
         model.allreduce_grads()
-    stepped = _grads_finite(model)   # identical on every rank after the all-reduce
     grad_norm = None
-    if stepped:
-        grad_norm = _host_clip(optimizer)
+    if ls is not None:
+        # the device decision of the gated path (scan; skip + zero, or unscale + clip + Adam +
+        # zero_grad), read back because this path reports a host bool
+        from .optim import G_STEPPED
         optimizer.step()
-        if grad_norm is None:   # FusedAdam with the option: the norm its own clip measured
-            grad_norm = getattr(optimizer, "last_grad_norm", None)
-        optimizer.zero_grad()
+        stepped = bool(optimizer._gate[G_STEPPED].item())
+        grad_norm = optimizer.last_grad_norm
+    elif gs is not None:
+        stepped, grad_norm = _scaled_step_host(model, optimizer, gs)
     else:
+        stepped = _grads_finite(model)   # identical on every rank after the all-reduce
+        if stepped:
+            grad_norm = _host_clip(optimizer)
+            optimizer.step()
+            if grad_norm is None:   # FusedAdam with the option: the norm its own clip measured
+                grad_norm = getattr(optimizer, "last_grad_norm", None)
+            optimizer.zero_grad()
+    if not stepped and used_scale is not None:
+        logging.warning(f"Skipping optimizer step: gradient overflow at loss scale "
+                        f"{float(used_scale):g}")
+    elif not stepped:
         logging.warning("Skipping optimizer step due to NaN/Inf gradients")
     r = dict(loss=loss.detach(), output=output, predicted=predicted, ce=ce.detach(),
              scaled_kl=scaled_kl.detach(), stepped=stepped)
     if grad_norm is not None:
         r["grad_norm"] = grad_norm
+    if used_scale is not None:
+        r["loss_scale"] = used_scale
     return r
 
 
@@ -308,7 +372,7 @@ class _TrainEpoch:
         self.pending = []
 
     def add(self, i, r, labels):
-        keep = ("loss", "ce", "scaled_kl", "ok_loss", "stepped", "grad_norm")
+        keep = ("loss", "ce", "scaled_kl", "ok_loss", "stepped", "grad_norm", "loss_scale")
         r = dict({k: r[k] for k in keep if k in r},
                  n_correct=(r["predicted"] == labels).sum(), n=labels.size(0))
         self.pending.append((i, r))
@@ -325,7 +389,11 @@ class _TrainEpoch:
             logging.warning(f"Skipping batch {i} due to NaN/Inf loss: {r['loss']}")
             return
         if "ok_loss" in r and not bool(r["stepped"]):   # (the host-decided path warned already)
-            logging.warning("Skipping optimizer step due to NaN/Inf gradients")
+            if "loss_scale" in r:
+                logging.warning(f"Skipping optimizer step: gradient overflow at loss scale "
+                                f"{float(r['loss_scale']):g}")
+            else:
+                logging.warning("Skipping optimizer step due to NaN/Inf gradients")
         lv = r["loss"].item()
         self.total_loss += lv
         self.correct += int(r["n_correct"].item())
@@ -334,6 +402,8 @@ class _TrainEpoch:
         self.writer.add_scalar("Loss/train", lv, i)
         if "grad_norm" in r:   # gradient clipping on: the pre-clip norm, NaN for a skipped step
             self.writer.add_scalar("GradNorm/train", float(r["grad_norm"]), i)
+        if "loss_scale" in r:  # loss scaling on: the scale this batch's backward ran with
+            self.writer.add_scalar("LossScale/train", float(r["loss_scale"]), i)
         logging.info(f"[Epoch {self.epoch} | Batch {i}] Loss: {lv:.4f}, "
                      f"Accuracy: {self.correct / max(self.total, 1):.4f}")
 
@@ -624,14 +694,29 @@ def train_unimodal_model(model, dataloader, criterion, optimizer, epoch, total_n
                     ce = criterion(output, labels)
                     predicted = output.detach().float().max(1)[1]
                 loss = ce + kl_w * (kl / dataloader.batch_size)
-                loss.backward()
-                _host_clip(optimizer)
-                optimizer.step()
+                # loss scaling: FusedAdam.step() decides on the device (and zeroes the
+                # gradients); a host model's GradScaler is driven in torch's order
+                ls = _fused_scaler(optimizer) if loss.is_cuda else None
+                gs = _host_scaler(optimizer)
+                if ls is not None:
+                    used_scale = ls.scale_tensor(loss.device).clone()[0]
+                    (loss * used_scale).backward()
+                    optimizer.step()
+                elif gs is not None:
+                    used_scale = torch.tensor(gs.get_scale())
+                    gs.scale(loss).backward()
+                    _scaled_step_host(model, optimizer, gs)
+                else:
+                    loss.backward()
+                    _host_clip(optimizer)
+                    optimizer.step()
                 lv = loss.item()
                 total_loss += lv
                 correct += int((predicted == labels).sum().item())
                 total += labels.size(0)
                 sum_writer.add_scalar("Loss/train", lv, i)
+                if ls is not None or gs is not None:
+                    sum_writer.add_scalar("LossScale/train", float(used_scale), i)
             train_accuracy = correct / total
             train_loss = total_loss / total
             lr = optimizer.param_groups[0]["lr"]
