@@ -477,6 +477,28 @@ int mauv_bn_bwd_mask(int dtype, const void* y, const unsigned char* mask, const 
                      const float* mean, const float* invstd, const float* scale, int G,
                      long long M, int C, float* workspace, void* dy, void* dres, float* dgamma,
                      float* dbeta, hipStream_t stream);
+/* Frozen BatchNorm: normalisation with the running statistics (module.eval()).
+ * mauv_bn_eval_stats is mauv_bn_eval_params (the same scale / shift bits) plus the two rows the
+ * backward's xhat needs, copied per group: mean[g][c] = run_mean[c],
+ * invstd[g][c] = 1 / sqrtf(run_var[c] + eps). */
+int mauv_bn_eval_stats(int G, int C, const float* gamma, const float* beta,
+                       const float* run_mean, const float* run_var, float eps, float* mean,
+                       float* invstd, float* scale, float* shift, hipStream_t stream);
+/* The backward of a BatchNorm whose statistics are constants of the step; the arguments are
+ * mauv_bn_bwd_ex's without pre_p1/pre_p2, dz and the ReLU source rules are its own:
+ *   dy = scale * dz (one fp32 product, one rounding to the storage type),  dres = dz (exact),
+ *   dgamma += sum dz * (y - mean) * invstd,  dbeta += sum dz  (over all groups);
+ * dy, dres, dgamma, dbeta each nullable.  dgamma and dbeta both NULL: one row-walk launch that
+ * reads dout once and, beside it, only the ReLU source (y only for y*scale + shift; mean, invstd
+ * and workspace may be NULL).  Otherwise one kernel sums mauv_bn_bwd_ex's partials (its geometry
+ * and order) while it stores dy / dres, and mauv_bn_bwd_ex's finalize and parameter kernels
+ * reduce them: no atomics, and dgamma / dbeta are the bits mauv_bn_bwd_ex accumulates for the
+ * same operands.  C % 8 == 0, C <= 2048; workspace: mauv_bn_workspace_floats. */
+int mauv_bn_bwd_frozen(int dtype, const void* y, const void* out, const unsigned char* mask,
+                       const void* dout, int relu, const float* mean, const float* invstd,
+                       const float* scale, const float* shift, int G, long long M, int C,
+                       float* workspace, void* dy, void* dres, float* dgamma, float* dbeta,
+                       hipStream_t stream);
 
 /* ---- pooling (pool.hip): torchvision stem maxpool 3x3/2 pad 1 and adaptive avgpool ------ */
 /* max-pool forward: C % 8 == 0 (the stem: 64); backward: C % 4 == 0. */

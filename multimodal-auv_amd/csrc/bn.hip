@@ -1002,3 +1002,254 @@ MAUV_API int mauv_bn_bwd_mask(int dtype, const void* y, const unsigned char* mas
   return bn_bwd_any("bn_bwd_mask", dtype, y, nullptr, dout, 1, mean, invstd, scale, nullptr, G, M,
                     C, workspace, dy, dres, dgamma, dbeta, nullptr, nullptr, 0, stream, mask);
 }
+
+// ---- Frozen BatchNorm: normalisation with the running statistics (module.eval(), mauv.frozen) ----
+// The statistics are constants of the step, so the batch terms of the training backward vanish:
+// dy = scale * dz, one pass over dout.  The parameter gradients keep their definition
+// (dbeta += sum dz, dgamma += sum dz * xhat with xhat from the stored mean / invstd) and the
+// training backward's partial geometry, per-thread order and finalize kernels, so they are the
+// bits mauv_bn_bwd_ex accumulates for the same operands.
+namespace mauv {
+
+// bn_eval_params_kernel's scale / shift (the same expressions) plus the rows the backward's xhat
+// needs: mean = run_mean, invstd = 1 / sqrt(run_var + eps), copied per group.
+__global__ void bn_eval_stats_kernel(int G, int C, const float* __restrict__ gamma,
+                                     const float* __restrict__ beta,
+                                     const float* __restrict__ rm, const float* __restrict__ rv,
+                                     float eps, float* __restrict__ mean,
+                                     float* __restrict__ invstd, float* __restrict__ scale,
+                                     float* __restrict__ shift) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  const float sc = gamma[c] / sqrtf(rv[c] + eps);
+  const float sh = beta[c] - rm[c] * sc;
+  const float mu = rm[c], is = 1.0f / sqrtf(rv[c] + eps);
+  for (int g = 0; g < G; ++g) {
+    mean[g * C + c] = mu;
+    invstd[g * C + c] = is;
+    scale[g * C + c] = sc;
+    shift[g * C + c] = sh;
+  }
+}
+
+// dz of 8 channels under ReLU source SRC (0 none, 1 mask bits m, 2 / 3: where p > 0, p the stored
+// output / y * scale + shift as the forward formed it)
+template <int SRC>
+__device__ __forceinline__ floatx8 relu_gate(floatx8 dz, unsigned m, const floatx8& p) {
+  if constexpr (SRC == 1) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) dz[e] = (m >> e) & 1u ? dz[e] : 0.f;
+  } else if constexpr (SRC >= 2) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) dz[e] = p[e] > 0.f ? dz[e] : 0.f;
+  }
+  return dz;
+}
+
+// gamma / beta frozen too: dy = scale * dz, dres = dz (each nullable) in one row walk
+// (bn_bwd_apply_rows' structure and geometry).  Reads dout once, and beside it only the ReLU
+// source: the mask byte, out, or — the lazily applied BN — y.
+template <class S>
+__global__ __launch_bounds__(256) void bn_bwd_frozen_rows(const typename S::T* __restrict__ y,
+                                                          const typename S::T* __restrict__ out,
+                                                          const typename S::T* __restrict__ dout,
+                                                          int relu,
+                                                          const float* __restrict__ scale,
+                                                          const float* __restrict__ shift,
+                                                          typename S::T* __restrict__ dy,
+                                                          typename S::T* __restrict__ dres,
+                                                          long long M, int C, int rpb,
+                                                          const unsigned char* __restrict__ mask) {
+  RowSlab t(C);
+  if (t.t_r >= t.rp) return;
+  t.slab(M, C, rpb);
+  const floatx8 sc = ldf8(scale + t.gc);
+  floatx8 sh = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (relu && !out && !mask) sh = ldf8(shift + t.gc);
+  constexpr int RU = 2;
+  auto rows = [&](auto src) {
+    constexpr int SRC = decltype(src)::value;  // 0 none, 1 mask bits, 2 out, 3 y*scale+shift
+    for (long long r = t.r0 + t.t_r; r < t.r1; r += RU * t.rp) {
+      typename S::R8 dr[RU], pr[RU];
+      unsigned m[RU];
+#pragma unroll
+      for (int u = 0; u < RU; ++u) {
+        const long long rr = r + (long long)u * t.rp;
+        const long long o = t.base + (rr < t.r1 ? rr : r) * C;   // past r1: row r again, not stored
+        dr[u] = S::raw8(dout + o);
+        if constexpr (SRC == 1) m[u] = mask[o >> 3];
+        if constexpr (SRC == 2) pr[u] = S::raw8(out + o);
+        if constexpr (SRC == 3) pr[u] = S::raw8(y + o);
+      }
+#pragma unroll
+      for (int u = 0; u < RU; ++u) {
+        const long long rr = r + (long long)u * t.rp;
+        floatx8 p = sh;
+        if constexpr (SRC == 2) p = S::cvt8(pr[u]);
+        if constexpr (SRC == 3) p = S::cvt8(pr[u]) * sc + sh;
+        const floatx8 dz = relu_gate<SRC>(S::cvt8(dr[u]), SRC == 1 ? m[u] : 0u, p);
+        if (rr < t.r1) {
+          const long long o = t.base + rr * C;
+          if (dy) S::st8(dy + o, sc * dz);
+          if (dres) S::st8(dres + o, dz);
+        }
+      }
+    }
+  };
+  if (mask) rows(std::integral_constant<int, 1>());
+  else if (!relu) rows(std::integral_constant<int, 0>());
+  else if (out) rows(std::integral_constant<int, 2>());
+  else rows(std::integral_constant<int, 3>());
+}
+
+// gamma / beta trainable: bn_bwd_partial's sums (its geometry, row order and expressions, so
+// p1 / p2 are its bits) by a kernel that also stores dy = scale * dz and dres = dz of the rows it
+// walks: dout and y are read once, not once for the sums and once for the apply.
+template <class S>
+__global__ __launch_bounds__(256) void bn_bwd_frozen_partial(
+    const typename S::T* __restrict__ y, const typename S::T* __restrict__ out,
+    const typename S::T* __restrict__ dout, int relu, const float* __restrict__ mean,
+    const float* __restrict__ invstd, const float* __restrict__ scale,
+    const float* __restrict__ shift, long long M, int C, int rpb, float* __restrict__ p1,
+    float* __restrict__ p2, typename S::T* __restrict__ dy, typename S::T* __restrict__ dres,
+    const unsigned char* __restrict__ mask) {
+  const int tpr = C / 8, rp = 256 / tpr;
+  const int g = blockIdx.y, blk = blockIdx.x, nblk = gridDim.x;
+  const int tid = threadIdx.x;
+  const int t_c = tid % tpr, t_r = tid / tpr;
+  const long long r0 = (long long)blk * rpb;
+  const long long r1 = min(M, r0 + rpb);
+  const long long go = (long long)g * M * C;
+  const int c0 = 8 * t_c, gc = g * C + c0;
+  floatx8 s1 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, s2 = s1;
+  if (t_r < rp) {
+    const floatx8 mu = ldf8(mean + gc), is = ldf8(invstd + gc), sc = ldf8(scale + gc);
+    floatx8 sh = s1;
+    if (relu && !out && !mask) sh = ldf8(shift + gc);
+    constexpr int RU = 4;
+    const floatx8 z8 = s1;
+    auto rows = [&](auto src) {
+      constexpr int SRC = decltype(src)::value;  // 0 none, 1 mask bits, 2 out, 3 y*scale+shift
+      for (long long r = r0 + t_r; r < r1; r += RU * rp) {
+        typename S::R8 yr[RU], dr[RU], pr[RU];
+        unsigned m[RU];
+#pragma unroll
+        for (int u = 0; u < RU; ++u) {
+          // rows past r1 re-read row r; they add zeros and store nothing
+          const long long rr = r + (long long)u * rp;
+          const long long o = go + (rr < r1 ? rr : r) * C + c0;
+          yr[u] = S::raw8(y + o);
+          dr[u] = S::raw8(dout + o);
+          if constexpr (SRC == 1) m[u] = mask[o >> 3];
+          if constexpr (SRC == 2) pr[u] = S::raw8(out + o);
+        }
+#pragma unroll
+        for (int u = 0; u < RU; ++u) {
+          const long long rr = r + (long long)u * rp;
+          const floatx8 yv = S::cvt8(yr[u]);
+          floatx8 dz = rr < r1 ? S::cvt8(dr[u]) : z8;
+          floatx8 p = sh;
+          if constexpr (SRC == 2) p = S::cvt8(pr[u]);
+          if constexpr (SRC == 3) p = yv * sc + sh;
+          dz = relu_gate<SRC>(dz, SRC == 1 ? m[u] : 0u, p);
+          s1 += dz;
+          s2 += dz * (yv - mu) * is;
+          if (rr < r1) {
+            const long long o = go + rr * C + c0;
+            if (dy) S::st8(dy + o, sc * dz);
+            if (dres) S::st8(dres + o, dz);
+          }
+        }
+      }
+    };
+    if (mask) rows(std::integral_constant<int, 1>());
+    else if (!relu) rows(std::integral_constant<int, 0>());
+    else if (out) rows(std::integral_constant<int, 2>());
+    else rows(std::integral_constant<int, 3>());
+  }
+  __shared__ float sh1[2048], sh2[2048];  // [rp][C], rp * C = 8 * 256
+  if (t_r < rp) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      sh1[t_r * C + c0 + e] = s1[e];
+      sh2[t_r * C + c0 + e] = s2[e];
+    }
+  }
+  __syncthreads();
+  for (int c = tid; c < C; c += 256) {
+    float a = 0.f, b = 0.f;
+    for (int r = 0; r < rp; ++r) { a += sh1[r * C + c]; b += sh2[r * C + c]; }
+    const long long o = ((long long)g * nblk + blk) * C + c;
+    p1[o] = a;
+    p2[o] = b;
+  }
+}
+
+template <class S>
+static int bn_bwd_frozen_impl(const typename S::T* y, const typename S::T* out,
+                              const typename S::T* dout, int relu, const float* mean,
+                              const float* invstd, const float* scale, const float* shift, int G,
+                              long long M, int C, float* workspace, typename S::T* dy,
+                              typename S::T* dres, float* dgamma, float* dbeta,
+                              hipStream_t stream, const unsigned char* mask) {
+  if (!dgamma && !dbeta) {
+    if (!dy && !dres) return 0;
+    int nblk, rpb;
+    rows_geometry(M, C, nblk, rpb);
+    hipLaunchKernelGGL(bn_bwd_frozen_rows<S>, dim3(nblk, G), dim3(256), 0, stream, y, out, dout,
+                       relu, scale, shift, dy, dres, M, C, rpb, mask);
+    return check_launch("bn_bwd_frozen");
+  }
+  int nblk, rpb;
+  bwd_geometry(M, C, nblk, rpb);
+  float* p1 = workspace;
+  float* p2 = p1 + (long long)G * nblk * C;
+  float* k1 = p2 + (long long)G * nblk * C;
+  float* k2 = k1 + (long long)G * C;
+  hipLaunchKernelGGL(bn_bwd_frozen_partial<S>, dim3(nblk, G), dim3(256), 0, stream, y, out, dout,
+                     relu, mean, invstd, scale, shift, M, C, rpb, p1, p2, dy, dres, mask);
+  // bwd_geometry gives at most 256 partials per channel: below kSegAbove, so mauv_bn_bwd_ex's
+  // single-launch finalize and its parameter kernel
+  hipLaunchKernelGGL(bn_bwd_final, dim3((C + 63) / 64, G), dim3(1024), 0, stream, G, nblk, C, M,
+                     p1, p2, k1, k2);
+  hipLaunchKernelGGL(bn_bwd_param_kernel, dim3((C + 255) / 256), dim3(256), 0, stream, G, C, M,
+                     k1, k2, dgamma, dbeta);
+  return check_launch("bn_bwd_frozen");
+}
+
+}  // namespace mauv
+
+// mauv_bn_eval_params plus the mean / invstd rows a frozen BatchNorm's backward reads.
+MAUV_API int mauv_bn_eval_stats(int G, int C, const float* gamma, const float* beta,
+                                const float* run_mean, const float* run_var, float eps,
+                                float* mean, float* invstd, float* scale, float* shift,
+                                hipStream_t stream) {
+  if (G <= 0 || C <= 0) { set_error("bn_eval_stats: bad shape"); return kErrArg; }
+  hipLaunchKernelGGL(bn_eval_stats_kernel, dim3((C + 255) / 256), dim3(256), 0, stream, G, C,
+                     gamma, beta, run_mean, run_var, eps, mean, invstd, scale, shift);
+  return check_launch("bn_eval_stats");
+}
+
+// The backward of a BatchNorm that normalised with fixed statistics (include/mauv.h):
+//   dz as in mauv_bn_bwd_ex, dy = scale * dz, dres = dz, dgamma += sum dz*xhat, dbeta += sum dz.
+MAUV_API int mauv_bn_bwd_frozen(int dtype, const void* y, const void* out,
+                                const unsigned char* mask, const void* dout, int relu,
+                                const float* mean, const float* invstd, const float* scale,
+                                const float* shift, int G, long long M, int C, float* workspace,
+                                void* dy, void* dres, float* dgamma, float* dbeta,
+                                hipStream_t stream) {
+  if (C <= 0 || !use_rows(C)) { set_error("bn_bwd_frozen: unsupported C (C % 8 != 0 or > 2048)"); return kErrArg; }
+  if (G <= 0 || M <= 0 || !dout || !scale) { set_error("bn_bwd_frozen: bad shape, or no dout / scale"); return kErrArg; }
+  if (mask) relu = 1, out = nullptr;
+  if (relu && !out && !mask && !(y && shift)) { set_error("bn_bwd_frozen: relu mask needs mask bits, out, or y and shift"); return kErrArg; }
+  if ((dgamma || dbeta) && !(y && mean && invstd && workspace)) { set_error("bn_bwd_frozen: dgamma / dbeta need y, mean, invstd and the workspace"); return kErrArg; }
+  if (dtype < 0)
+    return bn_bwd_frozen_impl<SF32>((const float*)y, (const float*)out, (const float*)dout, relu,
+                                    mean, invstd, scale, shift, G, M, C, workspace, (float*)dy,
+                                    (float*)dres, dgamma, dbeta, stream, mask);
+#define L(D) return bn_bwd_frozen_impl<S16<D>>((const u16*)y, (const u16*)out, (const u16*)dout, relu, \
+                                               mean, invstd, scale, shift, G, M, C, workspace,      \
+                                               (u16*)dy, (u16*)dres, dgamma, dbeta, stream, mask);
+  MAUV_DT_DISPATCH(dtype, "bn_bwd_frozen", L)
+#undef L
+}

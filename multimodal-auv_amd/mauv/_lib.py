@@ -66,6 +66,8 @@ SIGNATURES = {
     "mauv_bn_stats_workspace_floats": [I, I, I],
     "mauv_bn_apply": [P, P, P, P, P, P, I, P, I, LL, I, P],
     "mauv_bn_eval_params": [I, I, P, P, P, P, F, P, P, P],
+    "mauv_bn_eval_stats": [I, I, P, P, P, P, F, P, P, P, P, P],
+    "mauv_bn_bwd_frozen": [I, P, P, P, P, I, P, P, P, P, I, LL, I, P, P, P, P, P, P],
     "mauv_bn_bwd": [P, P, P, I, P, P, P, P, I, LL, I, P, P, P, P, P, P, P, I, P],
     "mauv_bn_apply_h16": [I, P, P, P, P, P, P, I, P, I, LL, I, P],
     "mauv_bn_bwd_h16": [I, P, P, P, I, P, P, P, P, I, LL, I, P, P, P, P, P, P],

@@ -538,9 +538,10 @@ class TrunkRunner(_Runner):
 
     def _dgrad_partials(self, rec, s):
         """fp32: a {p1, p2, nblk, y, ...} dict for conv2d_bwd_data(bn=...) — rec's data gradient
-        is the output gradient of BN s — or None (16-bit, or the switch off)."""
+        is the output gradient of BN s — or None (16-bit, the switch off, or a frozen BatchNorm,
+        whose backward sums no batch terms)."""
         if not BWD_PARTIALS_F32 or self.dt != torch.float32 or s is None or \
-                (s.out is not None and s.mask is None):
+                not s.batch_stats or (s.out is not None and s.mask is None):
             return None
         conv, x, xs, x_bn, w, B, H, W = rec
         G, Cin, Cout, k = self.G, conv.in_channels, conv.out_channels, _first(conv.kernel_size)
@@ -641,8 +642,10 @@ class TrunkRunner(_Runner):
         else:
             if ysh is not None:
                 raise RuntimeError("mauv: centred storage needs batch statistics (_centre)")
-            ops.bn_eval_params(G, C, bn.weight, bn.bias, bn.running_mean, bn.running_var,
-                               bn.eps, scale, shift)
+            # frozen BatchNorm: the running statistics, with the mean / invstd rows its backward
+            # reads (_bn_bwd); nothing is updated
+            ops.bn_eval_stats(G, C, bn.weight, bn.bias, bn.running_mean, bn.running_var,
+                              bn.eps, mean, invstd, scale, shift)
         out = mask = None
         if materialize:
             out = torch.empty_like(y)
@@ -659,10 +662,8 @@ class TrunkRunner(_Runner):
     def _bn_bwd(self, rec, dout, want_dres=False, mask=None, pre=None):
         """mask: ReLU-mask bits applied to dout (a downsample BN fed the block output's
         dres = dout * mask without that tensor); pre: the partial sums dout's data gradient
-        wrote (_dgrad_partials), so the partial pass is skipped."""
-        if not rec.batch_stats:
-            raise NotImplementedError("mauv: backward through eval-mode BN is not on the path "
-                                      "(the reference trains and predicts in .train())")
+        wrote (_dgrad_partials), so the partial pass is skipped.  A frozen BatchNorm (running
+        statistics) has dy = scale * dz: ops.bn_bwd_frozen, which takes no partials."""
         G, M, C, bn = self.G, rec.M, rec.C, rec.bn
         dy = torch.empty_like(rec.y)
         dres = torch.empty_like(rec.y) if want_dres else None
@@ -670,6 +671,11 @@ class TrunkRunner(_Runner):
         dg = bn.weight.grad if bn.weight.requires_grad else None
         db = bn.bias.grad if bn.bias.requires_grad else None
         s = rec.stats
+        if not rec.batch_stats:
+            ops.bn_bwd_frozen(rec.y, rec.out, mask if mask is not None else rec.mask, dout,
+                              1 if mask is not None else rec.relu, s[0], s[1], s[2], s[3], G, M,
+                              C, ws, dy, dres, dg, db)
+            return dy, dres
         ops.bn_bwd_ex(rec.y, rec.out, mask if mask is not None else rec.mask, dout,
                       1 if mask is not None else rec.relu, s[0], s[1], s[2], s[3], G, M, C, ws,
                       dy, dres, dg, db,

@@ -548,6 +548,44 @@ def _dt_code(t):
     return -1 if t.dtype == torch.float32 else H16[t.dtype]
 
 
+def bn_eval_stats(G, C, gamma, beta, run_mean, run_var, eps, mean, invstd, scale, shift):
+    """bn_eval_params plus the rows a frozen BatchNorm's backward reads: mean = run_mean,
+    invstd = 1 / sqrt(run_var + eps), per group."""
+    _f32(gamma, beta, run_mean, run_var, mean, invstd, scale, shift)
+    check(lib.mauv_bn_eval_stats(G, C, _p(gamma), _p(beta), _p(run_mean), _p(run_var), eps,
+                                 _p(mean), _p(invstd), _p(scale), _p(shift), stream()),
+          "bn_eval_stats")
+
+
+def bn_bwd_frozen(y, out, mask, dout, relu, mean, invstd, scale, shift, G, M, C, ws, dy,
+                  dres=None, dgamma=None, dbeta=None):
+    """bn_bwd_ex for a BatchNorm that normalised with fixed statistics: dy = scale * dz,
+    dres = dz, dgamma += sum dz * xhat, dbeta += sum dz (each nullable); the ReLU source as in
+    bn_bwd_ex."""
+    t = y if y is not None else dout
+    if t.dtype in H16:
+        _h16(t.dtype, y, out, dout, dy, dres)
+    else:
+        _f32(y, out, dout, dy, dres)
+    _f32(mean, invstd, scale, shift, ws, dgamma, dbeta)
+    if any(a is not None and a.numel() != G * M * C for a in (y, out, dout, dy, dres)) or \
+            any(a is not None and a.numel() != G * C for a in (mean, invstd, scale, shift)):
+        raise ValueError("bn_bwd_frozen: operand sizes do not match (G, M, C)")
+    if dgamma is not None or dbeta is not None:
+        if any(a is not None and a.numel() != C for a in (dgamma, dbeta)) or ws is None or \
+                ws.numel() < bn_workspace_floats(G, M, C):
+            raise ValueError("bn_bwd_frozen: dgamma / dbeta are [C] and need a workspace of "
+                             "bn_workspace_floats(G, M, C)")
+    if mask is not None:
+        _dev(torch.uint8, mask)
+        if mask.numel() * 8 != G * M * C:
+            raise ValueError("bn_bwd_frozen: mask size does not match (G, M, C)")
+    check(lib.mauv_bn_bwd_frozen(_dt_code(t), _p(y), _p(out), _p(mask), _p(dout), int(relu),
+                                 _p(mean), _p(invstd), _p(scale), _p(shift), G, M, C, _p(ws),
+                                 _p(dy), _p(dres), _p(dgamma), _p(dbeta), stream()),
+          "bn_bwd_frozen")
+
+
 def bn_apply_mask(y, scale, shift, res, out, mask, G, M, C, res_bn=None):
     """bn_apply with relu, also writing the ReLU mask bits of out: mask uint8 [G*M*C/8]."""
     rs, rh = res_bn if res_bn is not None else (None, None)
