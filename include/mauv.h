@@ -373,6 +373,43 @@ typedef struct MauvLossScale {
 int mauv_adam_step_ex_scaled(const MauvAdamEntryEx* table, int n, const MauvAdamGroup* groups,
                              int n_groups, MauvStepGate* gate, MauvLossScale* scaler,
                              hipStream_t stream);
+/* Gradient accumulation decided on the device: a window of micro-batches whose gradients sum in
+ * the arena and take ONE decision and one Adam step.  32-byte device struct beside the gate, as
+ * MauvLossScale; the caller zero-initialises it and, per micro-batch, writes gate->ok_loss and
+ * runs the backward (on loss * scale with a scaler: the scale cannot change inside a window).
+ * mauv_accum_note is a micro-batch that does not close its window, on one thread: micro += 1;
+ * if ok_loss == 0, bad_loss += 1 and gate->skipped_loss += 1; gate->stepped = 0, gate->mode = 0.
+ * It touches nothing else (not nonfinite, poisoned, the step count or a scaler); the caller runs
+ * no scan and no Adam launch for such a micro-batch. */
+typedef struct MauvAccum {      /* caller zero-initialises */
+  int micro;      /* micro-batches folded into the open window            (library) */
+  int bad_loss;   /* of those, how many had ok_loss == 0                  (library) */
+  float avg;      /* (float)(1.0 / micro) of the window just closed       (library) */
+  int windows, dropped;         /* windows closed; closed without a step on a bad loss */
+  int reserved[3];
+} MauvAccum;
+int mauv_accum_note(MauvStepGate* gate, MauvAccum* acc, hipStream_t stream);
+/* mauv_adam_step_ex_scaled closing a window (the caller has scanned the arena into the gate, as
+ * for every gated step).  acc == NULL: exactly mauv_adam_step_ex_scaled(table, n, groups,
+ * n_groups, gate, scaler, stream); scaler may be NULL either way.  Otherwise one thread folds this
+ * micro-batch in as mauv_accum_note does, forms avg = (float)(1.0 / (double)micro) and takes the
+ * decision of mauv_adam_step_ex_scaled (of mauv_adam_step_ex without a scaler) with "ok_loss" read
+ * as bad_loss == 0; then windows += 1, dropped += (bad_loss != 0), micro = bad_loss = 0.  So
+ *   any non-finite loss in the window -> the window is dropped whole: no step, the arena zeroed
+ *                     (mode 2) or left alone when poisoned (mode 0); the scaler is untouched
+ *   nonfinite != 0 -> as without a window: poisoned and kept without a scaler; zeroed and one
+ *                     backoff with one
+ *   otherwise      -> one Adam step; the growth tracker moves once per window
+ * With max_norm > 0 grad_norm becomes fl32(fl32(grad_norm * unscale) * avg), the norm of the
+ * averaged, unscaled gradient, and clip_coef is formed from it.  The Adam kernel loads each
+ * gradient as fl32(fl32(fl32(g * unscale) * avg) * clip_coef), each product rounded on its own,
+ * never contracted into the weight-decay term and never written back.  A window of one (a fresh
+ * MauvAccum) gives mauv_adam_step_ex_scaled's bits.  Argument errors (a null table / groups /
+ * gate, n outside 1..65535, n_groups outside 1..8; a null gate or acc for mauv_accum_note) return
+ * a negative code before any launch. */
+int mauv_adam_step_ex_accum(const MauvAdamEntryEx* table, int n, const MauvAdamGroup* groups,
+                            int n_groups, MauvStepGate* gate, MauvLossScale* scaler,
+                            MauvAccum* acc, hipStream_t stream);
 
 /* ---- global gradient norm + non-finite scan, in-place clip (gradnorm.hip) -------------------
  * torch.nn.utils.clip_grad_norm_ over a DEVICE table of fp32 spans: the flat gradient arena is

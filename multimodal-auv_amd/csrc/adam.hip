@@ -14,17 +14,23 @@
 // DESIGN.md §2.36; 1 when it is off).  mauv_adam_step_ex_scaled is the gated launch with dynamic
 // loss scaling (torch.amp.GradScaler's algorithm): the decision also backs the
 // scale off or grows it, and the kernel multiplies g by 1 / scale ahead of the clip coefficient.
+// mauv_accum_note / mauv_adam_step_ex_accum add gradient accumulation: a window
+// of micro-batches is counted in a MauvAccum beside the gate, the closing call takes the same
+// decision once per window and the kernel multiplies g by 1 / micro between the two factors.
 #include "mauv_common.h"
 
 using namespace mauv;
 
 namespace mauv {
 
-// One element of torch's Adam update (m, v, p updated in place).
+// One element of torch's Adam update (m, v, p updated in place).  The weight-decay term is
+// stated as the single rounding fl(wd * p + g): left as g + wd * p the compiler fused it in the
+// vector loops and the ungated kernels but rounded wd * p first in the gated kernels' scalar
+// loops, so one element's bits depended on its row's alignment and on the entry point.
 __device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, float omb1,
                                           float beta2, float omb2, float eps, float wd,
                                           float step_size, float bc2_sqrt) {
-  const float ge = wd != 0.f ? g + wd * p : g;
+  const float ge = wd != 0.f ? __builtin_fmaf(wd, p, g) : g;
   m = m + omb1 * (ge - m);
   v = v * beta2 + omb2 * ge * ge;
   p = p - step_size * (m / (sqrtf(v) / bc2_sqrt + eps));
@@ -117,15 +123,19 @@ __device__ __forceinline__ void gate_take_step(MauvStepGate* g, float lr, float 
 // and the non-finite counter is reset for the next scan.  Every decision also writes the clip
 // coefficient the Adam kernels multiply the gradient by: torch's clip_grad_norm_ formula over
 // the scan's grad_norm when max_norm > 0, else 1 (unused when the step is skipped).
-__global__ void step_gate_kernel(MauvStepGate* g, float lr, float beta1, float beta2) {
-  const int ok_loss = g->ok_loss != 0, ok_grad = g->nonfinite == 0;
+// `ok_loss`: the loss was finite (a window of micro-batches: every one of them); `loss_skips`:
+// what a bad loss adds to skipped_loss (1, or 0 when mauv_accum_note counted it already); `avg`:
+// 1, or 1 / micro of a closing window, which scales the scanned norm of the summed gradients.
+__device__ __forceinline__ void gate_decide(MauvStepGate* g, int ok_loss, int loss_skips,
+                                            float avg, float lr, float beta1, float beta2) {
+  const int ok_grad = g->nonfinite == 0;
   if (ok_loss && ok_grad) {
     gate_take_step(g, lr, beta1, beta2);
   } else {
     g->stepped = 0;
     if (!ok_loss) {
       g->mode = g->poisoned ? 0 : 2;
-      g->skipped_loss += 1;
+      g->skipped_loss += loss_skips;
     } else {
       g->mode = 0;
       g->poisoned = 1;
@@ -133,7 +143,16 @@ __global__ void step_gate_kernel(MauvStepGate* g, float lr, float beta1, float b
     }
   }
   g->nonfinite = 0;
-  g->clip_coef = g->max_norm > 0.f ? clip_coef(g->max_norm, g->grad_norm) : 1.0f;
+  if (g->max_norm > 0.f) {
+    if (avg != 1.0f) g->grad_norm = __fmul_rn(g->grad_norm, avg);
+    g->clip_coef = clip_coef(g->max_norm, g->grad_norm);
+  } else {
+    g->clip_coef = 1.0f;
+  }
+}
+
+__global__ void step_gate_kernel(MauvStepGate* g, float lr, float beta1, float beta2) {
+  gate_decide(g, g->ok_loss != 0, 1, 1.0f, lr, beta1, beta2);
 }
 
 // The same decision with a loss scaler beside the gate (one thread).  The
@@ -148,9 +167,10 @@ __global__ void step_gate_kernel(MauvStepGate* g, float lr, float beta1, float b
 // growth_interval == 0 is a static scale: only the counters move.  unscale = 1 / scale is formed
 // from the scale the backward ran with, before it changes; the scanned norm is the scaled
 // gradients', so grad_norm is rewritten as the true norm before the clip coefficient is formed.
-__global__ void step_gate_scaled_kernel(MauvStepGate* g, MauvLossScale* s, float lr, float beta1,
-                                        float beta2) {
-  const int ok_loss = g->ok_loss != 0, ok_grad = g->nonfinite == 0;
+__device__ __forceinline__ void gate_decide_scaled(MauvStepGate* g, MauvLossScale* s, int ok_loss,
+                                                   int loss_skips, float avg, float lr,
+                                                   float beta1, float beta2) {
+  const int ok_grad = g->nonfinite == 0;
   const float scale = s->scale;
   const float unscale = (float)(1.0 / (double)scale);
   const bool dynamic = s->growth_interval != 0;
@@ -158,7 +178,7 @@ __global__ void step_gate_scaled_kernel(MauvStepGate* g, MauvLossScale* s, float
   if (!ok_loss) {
     g->stepped = 0;
     g->mode = g->poisoned ? 0 : 2;
-    g->skipped_loss += 1;
+    g->skipped_loss += loss_skips;
   } else if (!ok_grad) {
     g->stepped = 0;
     g->mode = 2;
@@ -186,10 +206,45 @@ __global__ void step_gate_scaled_kernel(MauvStepGate* g, MauvLossScale* s, float
   g->nonfinite = 0;
   if (g->max_norm > 0.f) {
     g->grad_norm = __fmul_rn(g->grad_norm, unscale);   // (a NaN stays NaN)
+    if (avg != 1.0f) g->grad_norm = __fmul_rn(g->grad_norm, avg);
     g->clip_coef = clip_coef(g->max_norm, g->grad_norm);
   } else {
     g->clip_coef = 1.0f;
   }
+}
+
+__global__ void step_gate_scaled_kernel(MauvStepGate* g, MauvLossScale* s, float lr, float beta1,
+                                        float beta2) {
+  gate_decide_scaled(g, s, g->ok_loss != 0, 1, 1.0f, lr, beta1, beta2);
+}
+
+// ---- gradient accumulation -------------------------------------------------
+// A micro-batch that does not close its window (one thread): it is counted, a non-finite loss
+// is remembered, and the gate reports "no step" (no Adam launch follows).
+__global__ void accum_note_kernel(MauvStepGate* g, MauvAccum* a) {
+  a->micro += 1;
+  if (g->ok_loss == 0) {
+    a->bad_loss += 1;
+    g->skipped_loss += 1;
+  }
+  g->stepped = 0;
+  g->mode = 0;
+}
+
+// The closing micro-batch (one thread): folded in as above, then the decision of the kernels
+// above once for the window, "loss ok" being "no micro-batch of it had a non-finite loss".
+__global__ void step_gate_accum_kernel(MauvStepGate* g, MauvLossScale* s, MauvAccum* a, float lr,
+                                       float beta1, float beta2) {
+  const int bad_now = g->ok_loss == 0;
+  const int micro = a->micro + 1, bad = a->bad_loss + bad_now;
+  const float avg = (float)(1.0 / (double)micro);
+  a->avg = avg;
+  if (s) gate_decide_scaled(g, s, bad == 0, bad_now, avg, lr, beta1, beta2);
+  else gate_decide(g, bad == 0, bad_now, avg, lr, beta1, beta2);
+  a->windows += 1;
+  a->dropped += bad != 0;
+  a->micro = 0;
+  a->bad_loss = 0;
 }
 
 // ---- every option, several parameter groups (mauv_adam_step_ex) ------------------------------
@@ -203,16 +258,27 @@ struct AdamGroupsArg {
 };
 
 struct AdamConsts {
-  float omb1, beta2, omb2, eps, wd, decay, step_size, bc2_sqrt, clip, unscale;
+  float omb1, beta2, omb2, eps, wd, decay, step_size, bc2_sqrt, clip, unscale, avg;
 };
+
+// The gradient a gated step loads: unscaled, averaged over an accumulation window's
+// micro-batches, clipped; every factor is 1 when off (g * 1 is g).  Contraction is off for this
+// statement (__fmul_rn is a plain product here and could be fused): the three products are
+// rounded one by one and none of them is fused into the arithmetic that follows, so the element
+// equals the step on gradients multiplied in place, one factor at a time.
+__device__ __forceinline__ float loaded_grad(float g, float unscale, float avg, float clip) {
+#pragma clang fp contract(off)
+  return ((g * unscale) * avg) * clip;
+}
 
 // One element of torch's single-tensor Adam with the row's options; all off is adam_elem.
 template <bool AMS, bool MAXI, bool DEC>
 __device__ __forceinline__ void adam_elem_ex(float& p, float g, float& m, float& v, float& vmax,
                                              const AdamConsts& k) {
   // first, where torch's GradScaler.unscale_ and then clip_grad_norm_ work: on .grad before
-  // step(), each product rounded on its own; both factors are 1 when off (g * 1 is g)
-  g = __fmul_rn(__fmul_rn(g, k.unscale), k.clip);
+  // step(), with the 1 / micro of an accumulation window in between (the mean of the unscaled
+  // micro-batch gradients is what gets clipped)
+  g = loaded_grad(g, k.unscale, k.avg, k.clip);
   if (!AMS && !MAXI && !DEC) {
     adam_elem(p, g, m, v, k.omb1, k.beta2, k.omb2, k.eps, k.wd, k.step_size, k.bc2_sqrt);
     return;
@@ -221,7 +287,7 @@ __device__ __forceinline__ void adam_elem_ex(float& p, float g, float& m, float&
   float ge = g;
   if (k.wd != 0.f) {
     if (DEC) p = p * k.decay;
-    else ge = g + k.wd * p;
+    else ge = __builtin_fmaf(k.wd, p, g);   // one rounding, as adam_elem
   }
   m = m + k.omb1 * (ge - m);
   v = v * k.beta2 + k.omb2 * ge * ge;
@@ -282,7 +348,8 @@ template <bool GATED>
 __global__ __launch_bounds__(256) void adam_ex_kernel(const MauvAdamEntryEx* __restrict__ tab,
                                                       AdamGroupsArg ga, int n_groups,
                                                       const MauvStepGate* __restrict__ gate,
-                                                      const MauvLossScale* __restrict__ ls) {
+                                                      const MauvLossScale* __restrict__ ls,
+                                                      const MauvAccum* __restrict__ acc) {
   int mode = 1;
   if (GATED) {
     mode = gate->mode;
@@ -314,6 +381,7 @@ __global__ __launch_bounds__(256) void adam_ex_kernel(const MauvAdamEntryEx* __r
   k.bc2_sqrt = ga.bc2_sqrt[gi];
   k.clip = GATED ? gate->clip_coef : 1.0f;
   k.unscale = (GATED && ls) ? ls->unscale : 1.0f;   // written by step_gate_scaled_kernel
+  k.avg = (GATED && acc) ? acc->avg : 1.0f;         // written by step_gate_accum_kernel
   if (GATED && (mode & 1)) {   // as step_gate_kernel forms them, at the gate's count
     const int st = gate->step;
     const double bc1 = 1.0 - pow((double)beta1, (double)st);
@@ -390,10 +458,10 @@ MAUV_API int mauv_adam_step_ex(const MauvAdamEntryEx* table, int n, const MauvAd
     hipLaunchKernelGGL(step_gate_kernel, dim3(1), dim3(1), 0, stream, gate, groups[0].lr,
                        groups[0].beta1, groups[0].beta2);
     hipLaunchKernelGGL(adam_ex_kernel<true>, dim3(64, n), dim3(256), 0, stream, table, ga,
-                       n_groups, (const MauvStepGate*)gate, nullptr);
+                       n_groups, (const MauvStepGate*)gate, nullptr, nullptr);
   } else {
     hipLaunchKernelGGL(adam_ex_kernel<false>, dim3(64, n), dim3(256), 0, stream, table, ga,
-                       n_groups, nullptr, nullptr);
+                       n_groups, nullptr, nullptr, nullptr);
   }
   return check_launch("adam_step_ex");
 }
@@ -424,6 +492,45 @@ MAUV_API int mauv_adam_step_ex_scaled(const MauvAdamEntryEx* table, int n,
   hipLaunchKernelGGL(step_gate_scaled_kernel, dim3(1), dim3(1), 0, stream, gate, scaler,
                      groups[0].lr, groups[0].beta1, groups[0].beta2);
   hipLaunchKernelGGL(adam_ex_kernel<true>, dim3(64, n), dim3(256), 0, stream, table, ga,
-                     n_groups, (const MauvStepGate*)gate, (const MauvLossScale*)scaler);
+                     n_groups, (const MauvStepGate*)gate, (const MauvLossScale*)scaler, nullptr);
   return check_launch("adam_step_ex_scaled");
+}
+
+// A micro-batch inside an accumulation window (mauv.h): one single-thread launch, no scan and
+// no Adam launch.
+MAUV_API int mauv_accum_note(MauvStepGate* gate, MauvAccum* acc, hipStream_t stream) {
+  if (!gate || !acc) { set_error("accum_note: no gate / window state"); return kErrArg; }
+  hipLaunchKernelGGL(accum_note_kernel, dim3(1), dim3(1), 0, stream, gate, acc);
+  return check_launch("accum_note");
+}
+
+// The closing micro-batch of an accumulation window (mauv.h): the window's decision, then the
+// Adam launch reading 1 / micro between 1 / scale and the clip coefficient.  acc == NULL is
+// exactly mauv_adam_step_ex_scaled(table, n, groups, n_groups, gate, scaler, stream).
+MAUV_API int mauv_adam_step_ex_accum(const MauvAdamEntryEx* table, int n,
+                                     const MauvAdamGroup* groups, int n_groups,
+                                     MauvStepGate* gate, MauvLossScale* scaler, MauvAccum* acc,
+                                     hipStream_t stream) {
+  if (n <= 0 || n > 65535 || !table) {
+    set_error("adam_step_ex_accum: bad table size");
+    return kErrArg;
+  }
+  if (n_groups < 1 || n_groups > MAUV_ADAM_MAX_GROUPS || !groups) {
+    set_error("adam_step_ex_accum: 1..8 parameter groups");
+    return kErrArg;
+  }
+  if (!gate) { set_error("adam_step_ex_accum: no gate"); return kErrArg; }
+  if (!acc) return mauv_adam_step_ex_scaled(table, n, groups, n_groups, gate, scaler, stream);
+  AdamGroupsArg ga = {};
+  for (int i = 0; i < n_groups; ++i) {
+    ga.g[i] = groups[i];
+    ga.step_size[i] = 0.f;
+    ga.bc2_sqrt[i] = 1.f;
+  }
+  hipLaunchKernelGGL(step_gate_accum_kernel, dim3(1), dim3(1), 0, stream, gate, scaler, acc,
+                     groups[0].lr, groups[0].beta1, groups[0].beta2);
+  hipLaunchKernelGGL(adam_ex_kernel<true>, dim3(64, n), dim3(256), 0, stream, table, ga,
+                     n_groups, (const MauvStepGate*)gate, (const MauvLossScale*)scaler,
+                     (const MauvAccum*)acc);
+  return check_launch("adam_step_ex_accum");
 }

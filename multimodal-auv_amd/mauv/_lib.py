@@ -55,6 +55,8 @@ SIGNATURES = {
     "mauv_adam_step_gated": [P, I, F, F, F, F, F, P, P],
     "mauv_adam_step_ex": [P, I, P, I, LL, P, P],
     "mauv_adam_step_ex_scaled": [P, I, P, I, P, P, P],
+    "mauv_accum_note": [P, P, P],
+    "mauv_adam_step_ex_accum": [P, I, P, I, P, P, P, P],
     # gradnorm.hip
     "mauv_grad_norm_workspace_bytes": [I],
     "mauv_grad_norm": [P, I, I, P, P, P, P],
@@ -136,6 +138,12 @@ class MauvLossScale(ctypes.Structure):
     """include/mauv.h MauvLossScale: the device loss-scaler state (32 bytes)."""
     _fields_ = [("scale", F), ("unscale", F), ("growth_factor", F), ("backoff_factor", F),
                 ("growth_interval", I), ("growth_tracker", I), ("overflows", I), ("growths", I)]
+
+
+class MauvAccum(ctypes.Structure):
+    """include/mauv.h MauvAccum: the device state of a gradient-accumulation window (32 bytes)."""
+    _fields_ = [("micro", I), ("bad_loss", I), ("avg", F), ("windows", I), ("dropped", I),
+                ("reserved", I * 3)]
 
 
 class MauvError(RuntimeError):

@@ -64,6 +64,11 @@ class DistributedMC(nn.Module):
         self.n_overlapped = 0   # trunk slices all-reduced from the backward hook (cumulative)
         self.n_buckets = 0      # all-reduce calls of the gradient exchange (cumulative)
         self.elems_reduced = 0  # arena values exchanged (cumulative)
+        # gradient accumulation (mauv.train.mc_train_step sets it before each backward): while
+        # a window of micro-batches is open the arena only sums; the trunk-ready hook issues
+        # nothing and allreduce_grads() is not called until the closing micro-batch, whose
+        # backward overlaps the all-reduces of the accumulated slices as ever
+        self.window_open = False
         if overlap and self.world > 1:
             st.grad_ready_hook = self._trunk_ready
 
@@ -122,6 +127,8 @@ class DistributedMC(nn.Module):
     def _trunk_ready(self, trunk):
         """Engine hook (trunk stream current): all-reduce this trunk's arena slice now, unless
         the KL backward — which adds into every slice — has not been issued yet this step."""
+        if self.window_open:
+            return
         st = root_state(self.module)
         if st.kl_bwd_count <= self._kl_mark:   # the loops always add get_kl_loss (:114)
             return

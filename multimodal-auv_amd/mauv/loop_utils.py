@@ -11,7 +11,9 @@
                                             loss_scale ("dynamic", a number or a
                                             mauv.amp.LossScaler) turns loss scaling on:
                                             FusedAdam's device scaler, or for a host model a
-                                            torch.amp.GradScaler("cpu") hung on the optimizer)
+                                            torch.amp.GradScaler("cpu") hung on the optimizer;
+                                            grad_accumulation (an integer >= 1) turns gradient
+                                            accumulation on for either optimizer)
 * ``train_and_evaluate_unimodal_model``     loop_utils.py:65-159 (epochs ``range(1, n)``)
 * ``train_and_evaluate_multimodal_model``   loop_utils.py:162-250 (scheduler stepped after
                                             training AND after evaluation, as the reference)
@@ -23,7 +25,8 @@ import torch.nn as nn
 import torch.optim as optim
 
 from .amp import host_grad_scaler, own_loss_scaler
-from .optim import FusedAdam, check_max_grad_norm, check_grad_norm_type
+from .optim import (FusedAdam, check_max_grad_norm, check_grad_norm_type,
+                    check_grad_accumulation)
 from .train import (train_unimodal_model, evaluate_unimodal_model, train_multimodal_model,
                     evaluate_multimodal_model)
 
@@ -41,16 +44,18 @@ def define_optimizers_and_schedulers(models_dict, optimizer_params=None, schedul
         if all(p.is_cuda for p in params):
             # (each optimizer gets a loss scaler of its own, also from one LossScaler instance)
             return FusedAdam(params, **dict(kw, loss_scale=own_loss_scaler(kw.get("loss_scale"))))
-        # a host model: torch's Adam does not know the clipping and loss-scaling options; they
-        # ride on the optimizer as attributes and mc_train_step clips with torch before its
-        # step(), and drives the torch GradScaler around it
+        # a host model: torch's Adam does not know the clipping, loss-scaling and accumulation
+        # options; they ride on the optimizer as attributes and mc_train_step sums the window's
+        # gradients, clips with torch before its step(), and drives the torch GradScaler around it
         kw = dict(kw)
         clip = check_max_grad_norm(kw.pop("max_grad_norm", None))
         kind = check_grad_norm_type(kw.pop("grad_norm_type", 2.0))
         scaler = host_grad_scaler(kw.pop("loss_scale", None))
+        accumulation = check_grad_accumulation(kw.pop("grad_accumulation", None))
         opt = optim.Adam(params, **kw)
         opt.max_grad_norm, opt.grad_norm_type = clip, kind
         opt.grad_scaler = scaler
+        opt.grad_accumulation = accumulation
         return opt
     optimizers = {k: adam(models_dict[k], optimizer_params[k]) for k in _MODEL_KEYS}
     schedulers = {k: optim.lr_scheduler.StepLR(optimizers[k], **scheduler_params[k])

@@ -48,6 +48,18 @@ live parameters (``ok_loss`` = 1): it scans, unscales, clips, steps AND zeroes t
 advance Adam's step count, and nothing waits on the host.  Where the gated form cannot apply —
 parameters with different step counts, more than 8 groups — it raises a ValueError rather than
 step on scaled gradients.
+
+``grad_accumulation`` (None, or an integer >= 1) adds gradient accumulation to the gated form
+(DESIGN.md §2.39): a plain attribute like ``max_grad_norm``, reassignable between windows, no
+``param_groups`` key and not in ``state_dict()``.  With K > 1 ``step_gated(gate)`` closes a window
+every K-th call (or when told to, ``close=True``); the other calls queue ``mauv_accum_note`` only:
+no scan, no Adam launch.  The closing call takes the all-groups entry ``mauv_adam_step_ex_accum``:
+one decision for the window (a window holding any non-finite loss is dropped whole), the loss
+scaler moves once per window, and the kernel multiplies each gradient by 1 / micro-batches between
+1 / scale and the clip coefficient, so the step is Adam on the mean of the micro-batch gradients.
+``zero_grad()`` also abandons the open window.  The ungated ``step()`` and
+``mauv.amp.LossScaler.step(opt)`` in a user's own loop do not look at the option: such a loop
+divides its gradients itself.
 """
 import ctypes
 import math
@@ -64,6 +76,8 @@ GATE_WORDS = 16          # sizeof(MauvStepGate) / 4 (include/mauv.h)
 G_OK_LOSS, G_NONFINITE, G_POISONED, G_MODE, G_STEP, G_STEPPED, G_SKIP_LOSS, G_SKIP_GRAD = range(8)
 G_MAX_NORM, G_GRAD_NORM, G_CLIP_COEF, G_NORM_KIND = 10, 11, 12, 13   # fp32, fp32, fp32, int
 G_SCRATCH = 15           # a reserved word the training step counts non-finite inputs in
+ACC_WORDS = 8            # sizeof(MauvAccum) / 4
+A_MICRO, A_BAD_LOSS, A_AVG, A_WINDOWS, A_DROPPED = range(5)   # int, int, fp32, int, int
 MAX_GROUPS = 8           # MAUV_ADAM_MAX_GROUPS
 F_AMSGRAD, F_MAXIMIZE, F_DECOUPLED = 1, 2, 4
 EX = "ex"                # key of the all-groups table / fast entry (group 0 alone keeps key 0)
@@ -88,6 +102,15 @@ def check_grad_norm_type(v):
     if isinstance(v, bool) or not isinstance(v, numbers.Real) or v not in (2.0, math.inf):
         raise ValueError(f"grad_norm_type must be 2 or float('inf'), got {v!r}")
     return float(v)
+
+
+def check_grad_accumulation(v):
+    """``grad_accumulation``: None (off) or an integer >= 1 (1 is off too)."""
+    if v is None:
+        return None
+    if isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < 1:
+        raise ValueError(f"grad_accumulation must be None or an integer >= 1, got {v!r}")
+    return int(v)
 
 
 def _span_rows(grads):
@@ -133,7 +156,8 @@ class FusedAdam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
                  amsgrad=False, *, foreach=None, maximize=False, capturable=False,
                  differentiable=False, fused=None, decoupled_weight_decay=False,
-                 max_grad_norm=None, grad_norm_type=2.0, loss_scale=None, **unsupported):
+                 max_grad_norm=None, grad_norm_type=2.0, loss_scale=None,
+                 grad_accumulation=None, **unsupported):
         for k, v in unsupported.items():
             if v not in (None, False):
                 raise ValueError(f"FusedAdam: unsupported option {k}={v}")
@@ -147,6 +171,10 @@ class FusedAdam(torch.optim.Optimizer):
         self._gate_clip = (0.0, 0)   # (max_norm, norm_kind) the device gate holds
         # dynamic loss scaling (mauv.amp.LossScaler): a plain attribute too
         self.loss_scale = loss_scale
+        # gradient accumulation in the gated form: a plain attribute too
+        self.grad_accumulation = grad_accumulation
+        self._accum = None         # device MauvAccum (int32[8]) beside the gate
+        self._accum_micro = 0      # micro-batches of the open window (host count)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
                                       amsgrad=amsgrad, maximize=maximize, foreach=foreach,
                                       capturable=capturable, differentiable=differentiable,
@@ -188,6 +216,35 @@ class FusedAdam(torch.optim.Optimizer):
     @loss_scale.setter
     def loss_scale(self, v):
         self.__dict__["_loss_scale"] = as_loss_scaler(v)
+
+    @property
+    def grad_accumulation(self):
+        return self.__dict__.get("_grad_accumulation")
+
+    @grad_accumulation.setter
+    def grad_accumulation(self, v):
+        self.__dict__["_grad_accumulation"] = check_grad_accumulation(v)
+
+    def accumulating(self):
+        """Gradient accumulation is on (K > 1), or a window opened under it is still open."""
+        return (self.grad_accumulation or 1) > 1 or self.__dict__.get("_accum_micro", 0) > 0
+
+    def closes_window(self, close=None):
+        """Whether the next ``step_gated`` call closes its window: ``close`` when given, else
+        every ``grad_accumulation``-th call (always, when accumulation is off)."""
+        if not self.accumulating():
+            return True
+        if close is not None:
+            return bool(close)
+        return self._accum_micro + 1 >= (self.grad_accumulation or 1)
+
+    def zero_grad(self, set_to_none=True):
+        """torch's ``zero_grad``; it also abandons an open accumulation window: the host count
+        and, by a device fill, the window's micro / bad_loss words."""
+        super().zero_grad(set_to_none)
+        self._accum_micro = 0
+        if self._accum is not None:
+            self._accum[A_MICRO:A_BAD_LOSS + 1].zero_()
 
     def _scaler(self):
         """The loss scaler when it is set and enabled, else None."""
@@ -312,18 +369,25 @@ class FusedAdam(torch.optim.Optimizer):
         self._tables[key] = (ident, tab)
         return tab
 
-    def _launch_ex(self, tab, t, gate, scaler=None):
+    def _launch_ex(self, tab, t, gate, scaler=None, accum=None):
         """mauv_adam_step_ex over every launch of ``tab``; the groups' current lr, betas, eps,
         weight_decay and flags travel by value.  ``scaler``: the device MauvLossScale pointer of
-        a gated step with loss scaling (mauv_adam_step_ex_scaled; one launch)."""
+        a gated step with loss scaling (mauv_adam_step_ex_scaled; one launch).  ``accum``: the
+        device MauvAccum pointer of a gated step that closes an accumulation window
+        (mauv_adam_step_ex_accum, with or without a scaler; one launch)."""
         table, chunks = tab
-        assert scaler is None or (gate is not None and len(chunks) == 1)
+        assert (scaler is None and accum is None) or (gate is not None and len(chunks) == 1)
         for r0, n, gis in chunks:
             arr = (MauvAdamGroup * len(gis))()
             for a, gi in zip(arr, gis):
                 g = self.param_groups[gi]
                 a.lr, a.eps, a.weight_decay = g["lr"], g["eps"], g["weight_decay"]
                 (a.beta1, a.beta2), a.flags = g["betas"], _flags(g)
+            if accum is not None:
+                check(lib.mauv_adam_step_ex_accum(table.data_ptr() + 56 * r0, n,
+                                                  ctypes.addressof(arr), len(gis), gate, scaler,
+                                                  accum, ops.stream()), "adam_step_ex_accum")
+                continue
             if scaler is not None:
                 check(lib.mauv_adam_step_ex_scaled(table.data_ptr() + 56 * r0, n,
                                                    ctypes.addressof(arr), len(gis), gate, scaler,
@@ -549,16 +613,35 @@ class FusedAdam(torch.optim.Optimizer):
         return self._gate
 
     @torch.no_grad()
-    def step_gated(self, gate):
+    def step_gated(self, gate, close=None):
         """One step whose execution (step + zero_grad, restore, or nothing) the kernel reads
         from ``gate`` — no host synchronisation.  Every trainable parameter of every group must
-        hold a gradient (the model's arena views); frozen ones get no state and no step."""
+        hold a gradient (the model's arena views); frozen ones get no state and no step.
+
+        With ``grad_accumulation`` K > 1 each call is one micro-batch.  ``close=None`` closes the
+        window on every K-th call (a host count), ``close=True`` / ``False`` says so outright (a
+        loader's last batch closes a partial window, averaged by its true count).  A call that
+        does not close queues ``mauv_accum_note`` alone; the closing call is the step, through
+        the all-groups entry.  The ungated ``step()`` and ``mauv.amp.LossScaler.step(opt)`` in
+        a user's own loop ignore the option."""
         assert gate is self._gate, "step_gated: use the gate returned by FusedAdam.gate()"
+        accum = None
+        if self.accumulating():
+            closing = self.closes_window(close)
+            if self._accum is None or self._accum.device != gate.device:
+                self._accum = torch.zeros(ACC_WORDS, dtype=torch.int32, device=gate.device)
+            accum = self._accum
+            if not closing:
+                self._accum_micro += 1
+                check(lib.mauv_accum_note(gate.data_ptr(), accum.data_ptr(), ops.stream()),
+                      "accum_note")
+                return
+            self._accum_micro = 0
         from torch.optim import optimizer as _topt
         for hook in list(_topt._global_optimizer_pre_hooks.values()) + \
                 list(self._optimizer_step_pre_hooks.values()):
             hook(self, (self,), {})
-        self._step_gated(gate)
+        self._step_gated(gate, accum)
         # what torch.optim.Optimizer.step's wrapper records: an LR scheduler stepped after this
         # does not warn "lr_scheduler.step() before optimizer.step()"; step hooks still run
         self._opt_called = True
@@ -566,16 +649,17 @@ class FusedAdam(torch.optim.Optimizer):
                 list(_topt._global_optimizer_post_hooks.values()):
             hook(self, (self,), {})
 
-    def _step_gated(self, gate):
-        """step_gated without the step hooks (``step()`` runs them itself)."""
+    def _step_gated(self, gate, accum=None):
+        """step_gated without the step hooks (``step()`` runs them itself).  ``accum``: the
+        device MauvAccum of the accumulation window this step closes."""
         pairs = self._gate_live
         live = [p for p, _ in pairs]
         if any(p.grad is None for p in live):
             raise RuntimeError("step_gated: every parameter needs a gradient tensor")
         ls = self._scaler()
-        # with a loss scaler every layout takes the all-groups entry: one plain group there is
-        # adam_elem, the simple kernel's element
-        simple = self._simple() and ls is None
+        # with a loss scaler or an accumulation window every layout takes the all-groups entry:
+        # one plain group there is adam_elem, the simple kernel's element
+        simple = self._simple() and ls is None and accum is None
         if simple:
             group = self.param_groups[0]
             b1, b2 = group["betas"]
@@ -608,7 +692,8 @@ class FusedAdam(torch.optim.Optimizer):
                                            ops.stream()), "adam_step_gated")
         else:
             self._launch_ex(tab, 0, gate.data_ptr(),
-                            None if ls is None else ls.device_state(gate.device).data_ptr())
+                            None if ls is None else ls.device_state(gate.device).data_ptr(),
+                            None if accum is None else accum.data_ptr())
         self.last_grad_norm = None if self.max_grad_norm is None else \
             gate[G_GRAD_NORM:G_GRAD_NORM + 1].view(torch.float32).clone()[0]
         self._gate_dirty = True

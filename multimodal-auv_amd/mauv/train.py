@@ -86,7 +86,7 @@ def mc_logits(model, num_mc, *inputs):
 
 def _grads_finite(model):
     st = unwrap(model).__dict__.get("_mauv_state")
-    if st is not None and st.arena is not None and all(
+    if st is not None and st.arena is not None and st.arena.flat.is_cuda and all(
             p.grad is None or p.grad.data_ptr() == v.data_ptr()
             for p, v in zip(st.arena.params, st.arena.views)):
         return mchead.all_finite(st.arena.flat)
@@ -251,7 +251,40 @@ def _throttle(model):
     return q
 
 
-def mc_train_step(model, inputs_tuple, labels, criterion, optimizer, num_mc, batch_size, kl_w):
+def _accumulation(optimizer):
+    """The ``grad_accumulation`` an optimizer carries (FusedAdam's option; an attribute hung on
+    a host model's torch optimizer by define_optimizers_and_schedulers), 1 when off."""
+    return getattr(optimizer, "grad_accumulation", None) or 1
+
+
+class _HostWindow:
+    """The accumulation window of the host-decided path, kept on the optimizer: micro-batches
+    folded in, and whether one of them had a non-finite loss."""
+
+    def __init__(self):
+        self.micro, self.bad = 0, False
+
+
+def _host_window(optimizer):
+    """The optimizer's open host window when gradient accumulation is on (or a window opened
+    under it is still open), else None."""
+    w = optimizer.__dict__.get("_mauv_window")
+    if _accumulation(optimizer) > 1 or (w is not None and w.micro > 0):
+        if w is None:
+            w = optimizer.__dict__["_mauv_window"] = _HostWindow()
+        return w
+    return None
+
+
+def _average_grads(optimizer, m):
+    """One in-place multiply of every gradient by 1 / m (the window's true count)."""
+    grads = [p.grad for g in optimizer.param_groups for p in g["params"] if p.grad is not None]
+    if grads:
+        torch._foreach_mul_(grads, 1.0 / m)
+
+
+def mc_train_step(model, inputs_tuple, labels, criterion, optimizer, num_mc, batch_size, kl_w,
+                  close_window=None):
     """One reference training batch (multimodal.py:104-146): MC forward, KL, CE, NaN/Inf loss
     skip, backward, NaN/Inf gradient guard, optimizer step + zero_grad.
 
@@ -277,7 +310,22 @@ def mc_train_step(model, inputs_tuple, labels, criterion, optimizer, num_mc, bat
     bits.  A host model's torch optimizer carrying a ``torch.amp.GradScaler`` (``grad_scaler``,
     hung there by define_optimizers_and_schedulers) is driven in torch's order.  DistributedMC:
     the scan runs after ``allreduce_grads()``, so every rank sees the same arena, takes the same
-    decision and keeps the same scale; no collective is added."""
+    decision and keeps the same scale; no collective is added.
+
+    With ``grad_accumulation`` K > 1 on the optimizer each call is one
+    micro-batch of a window that closes on every K-th call, or where ``close_window`` says so
+    (True on a loader's last batch closes a partial window, averaged by its true count).  The
+    gradients sum in the arena; ``ok_loss`` is written (and MIN-reduced) per micro-batch; a call
+    that does not close runs no scan, no all-reduce and no Adam launch, only the one-thread
+    ``mauv_accum_note``.  The closing call decides once for the window: a window holding any
+    non-finite loss is dropped whole, otherwise Adam steps on the mean gradient (1 / count as
+    the kernel loads it), and the loss scale moves once per window.  The result gains the host
+    bool ``closed``; ``stepped`` is 0 and ``grad_norm`` absent on calls that do not close.  The
+    host-decided path has the same semantics on the host: gradients are summed, a non-finite
+    loss runs no backward and marks the window bad, and the close either zeroes the gradients
+    (bad window) or multiplies them by 1 / count once and then clips, unscales and steps as ever.
+    BatchNorm statistics, the Philox offset and the KL term (``KL / batch_size * kl_w``) are per
+    micro-batch."""
     inflight = _throttle(model)
     loss, output, predicted, ce, scaled_kl = mc_loss(model, inputs_tuple, labels, criterion,
                                                      num_mc, batch_size, kl_w)
@@ -287,18 +335,26 @@ def mc_train_step(model, inputs_tuple, labels, criterion, optimizer, num_mc, bat
     used_scale = None if ls is None else ls.scale_tensor(loss.device).clone()[0]
     if gate is not None:
         from .optim import G_OK_LOSS, G_NONFINITE, G_STEPPED, G_SCRATCH
+        accumulating = optimizer.accumulating()
+        closing = optimizer.closes_window(close_window)
         ok = gate[G_OK_LOSS:G_OK_LOSS + 1]
         ok.copy_(_batch_finite(loss, inputs_tuple, gate[G_SCRATCH:G_SCRATCH + 1]))
         if hasattr(model, "all_ranks_device"):
             model.all_ranks_device(ok)
+        if hasattr(model, "window_open"):   # DistributedMC exchanges the closing sums only
+            model.window_open = not closing
         (loss if ls is None else loss * used_scale).backward()
-        if hasattr(model, "allreduce_grads"):  # mauv.ddp.DistributedMC: RCCL all-reduce
-            model.allreduce_grads()
-        if optimizer.max_grad_norm is not None:
-            _scan_grad_norm(model, optimizer, gate)
+        if closing:
+            if hasattr(model, "allreduce_grads"):  # mauv.ddp.DistributedMC: RCCL all-reduce
+                model.allreduce_grads()
+            if optimizer.max_grad_norm is not None:
+                _scan_grad_norm(model, optimizer, gate)
+            else:
+                _count_nonfinite(model, gate[G_NONFINITE:G_NONFINITE + 1])
+        if accumulating:
+            optimizer.step_gated(gate, close=closing)
         else:
-            _count_nonfinite(model, gate[G_NONFINITE:G_NONFINITE + 1])
-        optimizer.step_gated(gate)
+            optimizer.step_gated(gate)
         flags = gate[:G_STEPPED + 1].clone() != 0   # this batch's decisions (device)
         if inflight is not None:
             ev = torch.cuda.Event()
@@ -307,11 +363,19 @@ def mc_train_step(model, inputs_tuple, labels, criterion, optimizer, num_mc, bat
         r = dict(loss=loss.detach(), output=output, predicted=predicted, ce=ce.detach(),
                  scaled_kl=scaled_kl.detach(), ok_loss=flags[G_OK_LOSS],
                  stepped=flags[G_STEPPED])
-        if optimizer.last_grad_norm is not None:
+        if accumulating:
+            r["closed"] = closing
+        if closing and optimizer.last_grad_norm is not None:
             r["grad_norm"] = optimizer.last_grad_norm
         if ls is not None:
             r["loss_scale"] = used_scale
         return r
+    win = _host_window(optimizer)
+    if win is not None:
+        return _host_window_step(model, inputs_tuple, loss, optimizer, win, close_window, ls,
+                                 used_scale, dict(loss=loss.detach(), output=output,
+                                                  predicted=predicted, ce=ce.detach(),
+                                                  scaled_kl=scaled_kl.detach()))
     if not _all_ranks(model, bool(_batch_finite(loss, inputs_tuple).item())):
         logging.warning(f"Skipping batch due to NaN/Inf loss: {loss}")
         return None
@@ -357,6 +421,68 @@ def mc_train_step(model, inputs_tuple, labels, criterion, optimizer, num_mc, bat
     return r
 
 
+def _host_window_step(model, inputs_tuple, loss, optimizer, win, close_window, ls, used_scale, r):
+    """One micro-batch of mc_train_step's host-decided path under gradient accumulation: the
+    gated path's semantics, decided on the host.  -> the result (``closed``, ``stepped``), or
+    None for a micro-batch whose loss was non-finite (it runs no backward and marks its window
+    bad; the window still closes on it when it is the last)."""
+    win.micro += 1
+    closing = bool(close_window) if close_window is not None else \
+        win.micro >= _accumulation(optimizer)
+    if hasattr(model, "window_open"):   # DistributedMC exchanges the closing sums only
+        model.window_open = not closing
+    finite = _all_ranks(model, bool(_batch_finite(loss, inputs_tuple).item()))
+    gs = _host_scaler(optimizer)
+    if not finite:
+        logging.warning(f"Skipping batch due to NaN/Inf loss: {loss}")
+        win.bad = True
+    elif ls is not None:
+        (loss * used_scale).backward()
+    elif gs is not None:
+        used_scale = torch.tensor(gs.get_scale())
+        gs.scale(loss).backward()
+    else:
+        loss.backward()
+    stepped, grad_norm = False, None
+    if closing:
+        m, bad = win.micro, win.bad
+        win.micro, win.bad = 0, False
+        if bad:
+            optimizer.zero_grad()   # the window is dropped whole
+        else:
+            if hasattr(model, "allreduce_grads"):  # DistributedMC: the window's sums, once
+                model.allreduce_grads()
+            _average_grads(optimizer, m)
+            if ls is not None:
+                from .optim import G_STEPPED
+                optimizer.step()
+                stepped = bool(optimizer._gate[G_STEPPED].item())
+                grad_norm = optimizer.last_grad_norm
+            elif gs is not None:
+                stepped, grad_norm = _scaled_step_host(model, optimizer, gs)
+            else:
+                stepped = _grads_finite(model)
+                if stepped:
+                    grad_norm = _host_clip(optimizer)
+                    optimizer.step()
+                    if grad_norm is None:
+                        grad_norm = getattr(optimizer, "last_grad_norm", None)
+                    optimizer.zero_grad()
+            if not stepped and used_scale is not None:
+                logging.warning(f"Skipping optimizer step: gradient overflow at loss scale "
+                                f"{float(used_scale):g}")
+            elif not stepped:
+                logging.warning("Skipping optimizer step due to NaN/Inf gradients")
+    if not finite:
+        return None
+    r.update(stepped=stepped, closed=closing)
+    if grad_norm is not None:
+        r["grad_norm"] = grad_norm
+    if used_scale is not None:
+        r["loss_scale"] = used_scale
+    return r
+
+
 class _TrainEpoch:
     """Per-batch bookkeeping of train_multimodal_model (multimodal.py:133-166) without a host
     round trip on the batch just issued: a batch's loss, correct count and skip decisions are
@@ -372,7 +498,8 @@ class _TrainEpoch:
         self.pending = []
 
     def add(self, i, r, labels):
-        keep = ("loss", "ce", "scaled_kl", "ok_loss", "stepped", "grad_norm", "loss_scale")
+        keep = ("loss", "ce", "scaled_kl", "ok_loss", "stepped", "grad_norm", "loss_scale",
+                "closed")
         r = dict({k: r[k] for k in keep if k in r},
                  n_correct=(r["predicted"] == labels).sum(), n=labels.size(0))
         self.pending.append((i, r))
@@ -388,7 +515,8 @@ class _TrainEpoch:
         if "ok_loss" in r and not bool(r["ok_loss"]):
             logging.warning(f"Skipping batch {i} due to NaN/Inf loss: {r['loss']}")
             return
-        if "ok_loss" in r and not bool(r["stepped"]):   # (the host-decided path warned already)
+        # (the host-decided path warned already; inside an accumulation window no step is due)
+        if "ok_loss" in r and r.get("closed", True) and not bool(r["stepped"]):
             if "loss_scale" in r:
                 logging.warning(f"Skipping optimizer step: gradient overflow at loss scale "
                                 f"{float(r['loss_scale']):g}")
@@ -486,6 +614,26 @@ def refresh_centres_on_gpu(model):
         refresh_centres(core)
 
 
+def _with_last(loader, look_ahead):
+    """(index, batch, is the last one) over ``loader``, the last one found by a one-batch
+    look-ahead (a loader need not have a length).  Without ``look_ahead`` (no accumulation
+    window to close) the loader is walked as ever and nothing is marked."""
+    if not look_ahead:
+        for i, batch in enumerate(loader):
+            yield i, batch, False
+        return
+    it = iter(loader)
+    try:
+        cur = next(it)
+    except StopIteration:
+        return
+    i = 0
+    for nxt in it:
+        yield i, cur, False
+        cur, i = nxt, i + 1
+    yield i, cur, True
+
+
 def train_multimodal_model(multimodal_model, dataloader, criterion, optimizer, epoch, device,
                            model_type, total_num_epochs, num_mc, sum_writer,
                            bathy_patch_type=None, sss_patch_type=None, csv_path=""):
@@ -506,11 +654,13 @@ def train_multimodal_model(multimodal_model, dataloader, criterion, optimizer, e
                             "cross entropy loss", "SSS Patch Type", "Channel Patch Type"])
             kl_w = kl_weight_for(epoch, total_num_epochs)
             ep = _TrainEpoch(epoch, sum_writer)
-            for i, batch in enumerate(dataloader):
+            for i, batch, last_batch in _with_last(dataloader, _accumulation(optimizer) > 1):
                 inputs, labels, bathy, sss = _batch_to(batch, device, bathy_patch_type,
                                                        sss_patch_type)
+                # gradient accumulation: the loader's last batch closes a partial window
                 r = mc_train_step(multimodal_model, (inputs, bathy, sss), labels, criterion,
-                                  optimizer, num_mc, dataloader.batch_size, kl_w)
+                                  optimizer, num_mc, dataloader.batch_size, kl_w,
+                                  close_window=True if last_batch else None)
                 if r is not None:
                     ep.add(i, r, labels)
             ep.flush()
@@ -677,13 +827,21 @@ def train_unimodal_model(model, dataloader, criterion, optimizer, epoch, total_n
             if new_file:
                 w.writerow(["Epoch", "Model type", "Loss", "Accuracy", "lr"])
             total_loss, correct, total = 0.0, 0, 0
-            for i, batch in enumerate(dataloader):
+            for i, batch, last_batch in _with_last(dataloader, _accumulation(optimizer) > 1):
                 if model_type not in _UNI_SOURCES:
                     logging.error(f"Unknown model_type: {model_type}")
                     raise ValueError(f"Unknown model_type: {model_type}")
                 x = batch[_UNI_SOURCES[model_type]].to(device, non_blocking=True)
                 labels = batch["label"].long().to(device, non_blocking=True)
-                optimizer.zero_grad()
+                # gradient accumulation (the host form): the gradients of a window's batches
+                # sum, and its last batch (every K-th, or the loader's last) averages and steps
+                win = _host_window(optimizer)
+                if win is None or win.micro == 0:
+                    optimizer.zero_grad()
+                closing = True
+                if win is not None:
+                    win.micro += 1
+                    closing = last_batch or win.micro >= _accumulation(optimizer)
                 logits = mc_logits(model, num_mc, x)
                 kl = get_kl_loss(model)
                 fused = _fused_ce(criterion, logits, labels)
@@ -701,15 +859,22 @@ def train_unimodal_model(model, dataloader, criterion, optimizer, epoch, total_n
                 if ls is not None:
                     used_scale = ls.scale_tensor(loss.device).clone()[0]
                     (loss * used_scale).backward()
-                    optimizer.step()
                 elif gs is not None:
                     used_scale = torch.tensor(gs.get_scale())
                     gs.scale(loss).backward()
-                    _scaled_step_host(model, optimizer, gs)
                 else:
                     loss.backward()
-                    _host_clip(optimizer)
-                    optimizer.step()
+                if closing:
+                    if win is not None:
+                        _average_grads(optimizer, win.micro)
+                        win.micro = 0
+                    if ls is not None:
+                        optimizer.step()
+                    elif gs is not None:
+                        _scaled_step_host(model, optimizer, gs)
+                    else:
+                        _host_clip(optimizer)
+                        optimizer.step()
                 lv = loss.item()
                 total_loss += lv
                 correct += int((predicted == labels).sum().item())
