@@ -590,6 +590,26 @@ int mauv_stem_fwd_h16(int dtype, const void* cols, const void* w, void* y, int G
                       int Cout, float* st_mean, float* st_m2, float* st_cnt, const float* y_shift,
                       hipStream_t stream);
 
+/* ---- the stems' data gradient (stem_dgrad.hip) --------------------------------------------
+ * d loss / d images through conv1, SUMMED over the G MC samples (they share the images), in two
+ * deterministic stages without atomics:
+ *   mauv_stem_bwd_rows_{f32,h16}: drows[m][k] = sum_g sum_co dy[g][m][co] w[g][co][k], one GEMM
+ *     M x Kp x (G*Cout) whose K loop runs over (g, co): the samples are summed in the fp32
+ *     accumulators.  dy [G][M][Cout] and w [G][Cout][Kp] (the forward's sampled weights, k >=
+ *     C*R*S zero) in fp32 (v_mfma_f32_32x32x2_f32) or dtype 0 = bf16 / 1 = f16
+ *     (v_mfma_f32_32x32x16_*); drows [M][Kp] is always fp32, its padded columns come out 0.
+ *     Kp % 8 == 0, Kp <= 2048, Cout % 8 == 0, M * Kp / 8 < 2^31; buffers 16-byte aligned.
+ *   mauv_stem_col2im: dx[b][c][ih][iw] (fp32 NCHW, the images' layout) = the sum, in a fixed
+ *     order, of drows[(b, oh, ow)][c*R*S + r*S + s] over the taps that reach the pixel — the
+ *     adjoint of mauv_stem_im2col's fp32 rows; columns k >= C*R*S are never read.
+ *     Kp >= C*R*S, B*C*H*W < 2^31. */
+int mauv_stem_bwd_rows_f32(const float* dy, const float* w, float* drows, int G, int M, int Kp,
+                           int Cout, hipStream_t stream);
+int mauv_stem_bwd_rows_h16(int dtype, const void* dy, const void* w, float* drows, int G, int M,
+                           int Kp, int Cout, hipStream_t stream);
+int mauv_stem_col2im(const float* drows, int B, int C, int H, int W, int R, int S, int stride,
+                     int pad, int Kp, float* dx, hipStream_t stream);
+
 /* ---- fusion head + MC head (head.hip) ----------------------------------------------------
  * AdditiveAttention.forward (models/base_models.py:43-52) epilogues around the q|k|v and
  * score GEMMs (qkv rows [q | k | v], each hid wide; the reference's model: hid = 128):

@@ -93,6 +93,10 @@ SIGNATURES = {
     "mauv_stem_im2col": [I, P] + [I] * 9 + [P, P],
     "mauv_stem_fwd_f32": [P, P, P, I, I, I, I, P, P, P, P],
     "mauv_stem_fwd_h16": [I, P, P, P, I, I, I, I, P, P, P, P, P],
+    # stem_dgrad.hip
+    "mauv_stem_bwd_rows_f32": [P, P, P, I, I, I, I, P],
+    "mauv_stem_bwd_rows_h16": [I, P, P, P, I, I, I, I, P],
+    "mauv_stem_col2im": [P] + [I] * 9 + [P, P],
     # head.hip
     "mauv_attn_t": [P, I, I, P, P],
     "mauv_attn_t_bwd": [P, P, I, I, P, P],

@@ -214,6 +214,14 @@ class RootState:
         return s
 
     def grads(self, device):
+        # a backward for input gradients alone (every parameter frozen) writes no parameter
+        # gradient: no arena is made (it would lack the tensors unfrozen later) and no p.grad is
+        # attached.  (any() stops at the first trainable tensor: one test on a training step.)
+        # An arena, once made, holds the tensors that trained then: after changing which
+        # parameters train, call invalidate(root) so that the next backward builds a new one.
+        live = self.params if self.arena is None else self.arena.params
+        if not any(p.requires_grad for p in live):
+            return None
         if self.arena is None or self.arena.flat.device != device:
             self.arena = GradArena(self.params, device)
         self.arena.ensure()
@@ -271,12 +279,15 @@ class _Engine(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, *grads):
         runner, ctx.runner = ctx.runner, None
+        runner.needs_input_grad = ctx.needs_input_grad[2:]   # of the runner's inputs
         gins = runner.run_backward(*grads)
         return (None, None) + tuple(gins)
 
 
 # ----------------------------------------------------------------------------- base runner
 class _Runner:
+    needs_input_grad = None   # set by _Engine.backward: which inputs autograd wants a gradient for
+
     def __init__(self, state, G, sample0, save):
         self.st, self.G, self.s0, self.save = state, G, sample0, save
 
@@ -455,11 +466,14 @@ class TrunkRunner(_Runner):
       backward rebuilds the ReLU mask from y.
     """
 
-    def __init__(self, trunk, state, G, sample0, save, dtype=torch.float32, join=None):
+    def __init__(self, trunk, state, G, sample0, save, dtype=torch.float32, join=None,
+                 input_grad=False):
         super().__init__(state, G, sample0, save)
         self.trunk = trunk
         self.join = join  # caller's stream when this trunk runs on a stream of its own
         self.dt = dtype   # activation / sampled-weight storage (fp32, bf16 or f16)
+        # the images require grad: the stem record keeps its sampled weights for _stem_dgrad
+        self.input_grad = input_grad
 
     def _centre(self, bn):
         """The centre the 16-bit conv feeding ``bn`` stores its output around (CENTRE_Y): bn's
@@ -596,13 +610,26 @@ class TrunkRunner(_Runner):
         part = (buf[:G * nblk * Cout], buf[G * nblk * Cout:2 * G * nblk * Cout],
                 buf[2 * G * nblk * Cout:], nblk)
         ops.stem_fwd(cols, w, y, G, M, Kp, Cout, part[:3], K, ysh=ysh)
-        rec = ("stem", conv, cols, M, Kp) if self.save else None
+        rec = ("stem", conv, cols, M, Kp, w if self.input_grad else None, (B, H, W)) \
+            if self.save else None
         return y, rec, part
+
+    def _stem_dgrad(self, rec, dy):
+        """d loss / d images, summed over the G samples: dy -> the rows' gradient (one GEMM over
+        the forward's sampled weights, fp32 out) -> col2im into the fp32 NCHW layout of the
+        caller's images (ops.stem_bwd_rows, ops.stem_col2im)."""
+        _, conv, _, M, Kp, w, (B, H, W) = rec
+        Cin, Cout, k = conv.in_channels, conv.out_channels, _first(conv.kernel_size)
+        drows = torch.empty(M, Kp, device=dy.device)
+        ops.stem_bwd_rows(dy, w, drows, self.G, M, Kp, Cout, Cin * k * k)
+        dx = torch.empty(B, Cin, H, W, device=dy.device)
+        ops.stem_col2im(drows, B, Cin, H, W, k, _first(conv.stride), _first(conv.padding), Kp, dx)
+        return dx
 
     def _stem_bwd(self, rec, dy):
         """Weight gradient of _stem: a 1x1 weight-gradient GEMM over the shared rows (group
         stride 0), then the reparameterisation backward over the [Cout][Kp] slabs."""
-        _, conv, cols, M, Kp = rec
+        _, conv, cols, M, Kp = rec[:5]
         if not conv.mu_kernel.requires_grad:
             return
         G, Cin, Cout, k = self.G, conv.in_channels, conv.out_channels, conv.kernel_size
@@ -834,11 +861,18 @@ class TrunkRunner(_Runner):
         self._stem_bwd(rc, dy0)
         if self.st.grad_ready_hook is not None:
             self.st.grad_ready_hook(self.trunk)
+        # the images' gradient, only when autograd asks for it (rank-local: after the hook)
+        dx = None
+        if self.input_grad and self.needs_input_grad is not None and self.needs_input_grad[0]:
+            dx = self._stem_dgrad(rc, dy0)
+        del dy0, rc
         if self.join is not None:   # the caller's stream (optimizer, all-reduce) waits for us
             ev = torch.cuda.Event()
             ev.record()
             self.join.wait_event(ev)
-        return (None,)
+            if dx is not None:   # produced on this trunk's stream, consumed behind the event
+                dx.record_stream(self.join)
+        return (dx,)
 
 
 # ----------------------------------------------------------------------------- head
@@ -1006,8 +1040,9 @@ def run_trunk_mc(trunk, x, num_mc, state=None, sample0=None, join=None):
         raise RuntimeError("mauv: the model must be on a ROCm device (model.to('cuda'))")
     s0 = st.next_samples(num_mc) if sample0 is None else sample0
     params = st.plist(("trunk", id(trunk)), lambda: list(trunk.parameters()))
-    save = needs_grad(params)
-    runner = TrunkRunner(trunk, st, num_mc, s0, save, st.trunk_dtype(), join)
+    want_dx = torch.is_grad_enabled() and x.requires_grad
+    save = needs_grad(params) or want_dx
+    runner = TrunkRunner(trunk, st, num_mc, s0, save, st.trunk_dtype(), join, want_dx)
     x = _to_device(x, dev)
     if x.dtype != torch.float32:   # autocast callers may hand 16-bit images; stems read fp32
         x = x.float()

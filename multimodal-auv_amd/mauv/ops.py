@@ -728,6 +728,44 @@ def stem_fwd(cols, w, y, G, M, Kp, Cout, stats, alg_k, ysh=None):
                                     _p(sn), stream()), "stem_fwd_f32")
 
 
+# ----------------------------------------------------- the stems' data gradient (stem_dgrad.hip)
+def stem_bwd_rows(dy, w, drows, G, M, Kp, Cout, alg_k):
+    """drows[M][Kp] (always fp32) = sum_g dy[g][M][Cout] . w[g][Cout][Kp]: the gradient of the
+    stem's im2col rows, summed over the G samples inside one GEMM (its K loop runs over (g, co)).
+    dy and w in the trunk dtype (fp32 / bf16 / f16).  alg_k: the stem's real Cin*R*S."""
+    _f32(drows)
+    if dy.numel() != G * M * Cout or w.numel() != G * Cout * Kp or drows.numel() != M * Kp:
+        raise ValueError(f"stem_bwd_rows: dy [G][M][Cout], w [G][Cout][Kp], drows [M][Kp] expected "
+                         f"for G={G}, M={M}, Kp={Kp}, Cout={Cout}, got {tuple(dy.shape)}, "
+                         f"{tuple(w.shape)}, {tuple(drows.shape)}")
+    fl = 2.0 * G * M * Cout * alg_k
+    nb = w.element_size() * (G * M * Cout + G * Cout * Kp) + 4.0 * M * Kp
+    if w.dtype in H16:
+        _h16(w.dtype, dy, w)
+        with _Prof("dgrad_" + str(w.dtype)[6:], fl, nb, info=("stem", G, M, Kp, Cout)):
+            check(lib.mauv_stem_bwd_rows_h16(H16[w.dtype], _p(dy), _p(w), _p(drows), G, M, Kp,
+                                             Cout, stream()), "stem_bwd_rows_h16")
+        return
+    _f32(dy, w)
+    with _Prof("dgrad", fl, nb, info=("stem", G, M, Kp, Cout)):
+        check(lib.mauv_stem_bwd_rows_f32(_p(dy), _p(w), _p(drows), G, M, Kp, Cout, stream()),
+              "stem_bwd_rows_f32")
+
+
+def stem_col2im(drows, B, C, H, W, R, stride, pad, Kp, dx):
+    """dx[B][C][H][W] (fp32 NCHW) from drows[B*Ho*Wo][Kp]: every pixel sums, in a fixed order,
+    the taps k = c*R*R + r*R + s that reach it — the adjoint of stem_im2col's fp32 rows."""
+    _f32(drows, dx)
+    Ho, Wo = out_hw(H, R, stride, pad), out_hw(W, R, stride, pad)
+    if drows.numel() != B * Ho * Wo * Kp or dx.numel() != B * C * H * W:
+        raise ValueError(f"stem_col2im: drows [{B * Ho * Wo}][{Kp}] and dx [{B}][{C}][{H}][{W}] "
+                         f"expected, got {tuple(drows.shape)} and {tuple(dx.shape)}")
+    nb = 4.0 * (B * Ho * Wo * C * R * R + B * C * H * W)
+    with _Prof("col2im", 0.0, nb, info=("stem", B, C, H, W, R, stride, pad, Kp)):
+        check(lib.mauv_stem_col2im(_p(drows), B, C, H, W, R, R, stride, pad, Kp, _p(dx),
+                                   stream()), "stem_col2im")
+
+
 # ----------------------------------------------------------------------- head
 def attn_t(qkv, rows, hid, t):
     _dev(torch.float32, qkv, t)
