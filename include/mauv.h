@@ -725,6 +725,53 @@ int mauv_resize_u8(const unsigned char* x, int B, int H, int W, int C, int Ho, i
                    const float* uifm_bt, const float* uifm_binf, const float* dist, float depth,
                    float* out_f32, hipStream_t stream);
 
+/* ---- on-device augmentation of co-registered tiles (staging.hip) ---------
+ * A move code is one byte per item, low 3 bits: bit0 = flip W, bit1 = flip H, bit2 = transpose
+ * H <-> W applied last (the dihedral group of the square).  As a gather on fp32 NCHW:
+ *   out[b][c][h][w] = v[b][c][h'][w'],  (p, q) = bit2 ? (w, h) : (h, w),
+ *   h' = bit1 ? H - 1 - p : p,  w' = bit0 ? W - 1 - q : q
+ * where v is what the un-augmented entry computes (Resize, ToTensor, Normalize and UIFM are
+ * evaluated at the source pixel, the distance map dist[b][h'][w'] included).  The inverse of
+ * code k is k when bit2 is clear, else k with bit0 and bit1 swapped.
+ *
+ * mauv_augment_draw: for item i = item0 + b,
+ *   r = philox4x32_10(ctr = (i, step lo32, 0x41554721, step hi32), key = seed)
+ * ops_out[b] = 0 (mode 0), r.x >> 30 (mode 1, flips) or r.x >> 29 (mode 2, dihedral);
+ * turb_out[b] (nullable) = turb_lo + (turb_hi - turb_lo) * u, u = ((float)r.y + 0.5f) * 2^-32,
+ * every operation rounded separately in fp32 (u can round to 1: turb lies in [lo, hi]).
+ * Refused: mode outside 0..2, turb_hi < turb_lo, B < 0, item0 < 0 or item0 + B > 2^32.
+ *
+ * The *_aug staging entries take the arguments of their plain entry plus ops (u8 [B],
+ * nullable = no move), turb (f32 [B], nullable) and allow_transpose.  With turb given the
+ * uifm_bt / beta argument holds the plain beta[c] and the kernel forms beta[c] * turb[b] as one
+ * fp32 product (the product the host forms for the plain entries: equal turbidities give the
+ * plain entry's bits); turb goes with an fp32 output only.  allow_transpose != 0 needs a square
+ * output tile (H == W; Ho == Wo for the resize) and is refused otherwise; with
+ * allow_transpose == 0 only bits 0 and 1 of a code are read, so no code indexes outside a
+ * non-square tile.  ops == NULL and turb == NULL run the plain entry's kernel.  The resize
+ * entry applies the move where its last pass stores (8-bit or fused fp32 output).
+ * mauv_stage_f32_aug: fp32 NCHW in and out, beta == NULL = a pure move.  A move is a gather, so
+ * an x that overlaps the output in any byte is refused: always by mauv_stage_f32_aug, and by the
+ * other two entries when ops are given.  Extents are refused by name (B < 0, C < 1, H or W < 1, an element
+ * count of 2^62 or more). */
+int mauv_augment_draw(unsigned long long seed, unsigned long long step, long long item0, int B,
+                      int mode, float turb_lo, float turb_hi, unsigned char* ops_out,
+                      float* turb_out, hipStream_t stream);
+int mauv_stage_u8_aug(const unsigned char* x, int B, int H, int W, int C, const float* mean,
+                      const float* stdv, const float* uifm_bt, const float* uifm_binf,
+                      const float* dist, float depth, const unsigned char* ops,
+                      const float* turb, int allow_transpose, float* out, hipStream_t stream);
+int mauv_resize_u8_aug(const unsigned char* x, int B, int H, int W, int C, int Ho, int Wo,
+                       void* workspace, unsigned char* out_u8, const float* mean,
+                       const float* stdv, const float* uifm_bt, const float* uifm_binf,
+                       const float* dist, float depth, const unsigned char* ops,
+                       const float* turb, int allow_transpose, float* out_f32,
+                       hipStream_t stream);
+int mauv_stage_f32_aug(const float* x, int B, int C, int H, int W, const float* beta,
+                       const float* binf, const float* dist, float depth,
+                       const unsigned char* ops, const float* turb, int allow_transpose,
+                       float* out, hipStream_t stream);
+
 /* ---- evaluation metrics (metrics.hip) ----------------------------------------------------
  * train/multimodal.py:312-347 (confusion matrix) and Examples/"Example training with image
  * noise.py":530-634 (uncertainty-error AUROC, macro F1, 15-bin ECE / Emax), accumulated on the

@@ -115,6 +115,10 @@ SIGNATURES = {
     "mauv_uifm": [P, I, I, I, I, P, P, P, F, P, P],
     "mauv_resize_workspace_bytes": [I, I, I, I, I, I],
     "mauv_resize_u8": [P, I, I, I, I, I, I, P, P, P, P, P, P, P, F, P, P],
+    "mauv_augment_draw": [U64, U64, LL, I, I, F, F, P, P, P],
+    "mauv_stage_u8_aug": [P, I, I, I, I, P, P, P, P, P, F, P, P, I, P, P],
+    "mauv_resize_u8_aug": [P, I, I, I, I, I, I, P, P, P, P, P, P, P, F, P, P, I, P, P],
+    "mauv_stage_f32_aug": [P, I, I, I, I, P, P, P, F, P, P, I, P, P],
     # metrics.hip
     "mauv_confusion_update": [P, P, I, I, P, P],
     "mauv_calibration_update": [P, P, I, I, I, P, P, P],

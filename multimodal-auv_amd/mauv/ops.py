@@ -906,3 +906,77 @@ def grad_clip(spans, norm, max_norm):
     _dev(torch.int64, spans)
     _dev(torch.float32, norm)
     check(lib.mauv_grad_clip(_p(spans), spans.shape[0], _p(norm), max_norm, stream()), "grad_clip")
+
+
+# ------------------------------------------------------------------ staging.hip: augmentation
+def _aug_operands(B, C, HW, ops_, turb, dist, per_channel):
+    """The per-item and per-channel operands of an augmented staging call hold what the kernel
+    reads: ops / turb one value per item, dist one per output pixel, the others one per channel."""
+    _dev(torch.uint8, ops_)
+    _dev(torch.float32, turb, dist, *per_channel)
+    for name, t, n in (("ops", ops_, B), ("turb", turb, B), ("dist", dist, B * HW)):
+        if t is not None and t.numel() != n:
+            raise ValueError(f"{name} must hold {n} values, got {t.numel()}")
+    for t in per_channel:
+        if t is not None and t.numel() != C:
+            raise ValueError(f"a per-channel operand must hold C = {C} values, got {t.numel()}")
+
+
+def augment_draw(seed, step, item0, mode, turb_lo, turb_hi, ops_out, turb_out=None):
+    """ops_out[b] (uint8) and turb_out[b] (fp32, optional) of items item0 + b from Philox keyed
+    by (seed, step); mode 0 none, 1 flips, 2 dihedral (include/mauv.h).  No host sync."""
+    _dev(torch.uint8, ops_out)
+    _dev(torch.float32, turb_out)
+    B = ops_out.numel()
+    if turb_out is not None and turb_out.numel() != B:
+        raise ValueError("turb_out must hold one value per item of ops_out")
+    check(lib.mauv_augment_draw(seed & (2 ** 64 - 1), step & (2 ** 64 - 1), item0, B, mode,
+                                turb_lo, turb_hi, _p(ops_out), _p(turb_out), stream()),
+          "augment_draw")
+
+
+def stage_u8_aug(x, mean, std, beta, binf, dist, depth, ops_, turb, allow_transpose, out):
+    """mauv_stage_u8 of uint8 [B, H, W, C] tiles into fp32 [B, C, H, W] with the per-item move
+    ``ops_`` applied in the same pass; with ``turb`` the UIFM uses beta[c] * turb[b]."""
+    _dev(torch.uint8, x)
+    B, H, W, C = x.shape
+    _dev(torch.float32, out)
+    if out.numel() != x.numel():
+        raise ValueError("out must be fp32 [B, C, H, W]")
+    _aug_operands(B, C, H * W, ops_, turb, dist, (mean, std, beta, binf))
+    check(lib.mauv_stage_u8_aug(_p(x), B, H, W, C, _p(mean), _p(std), _p(beta), _p(binf),
+                                _p(dist), depth, _p(ops_), _p(turb), int(bool(allow_transpose)),
+                                _p(out), stream()), "stage_u8_aug")
+
+
+def resize_u8_aug(x, Ho, Wo, workspace, out_u8, mean, std, beta, binf, dist, depth, ops_, turb,
+                  allow_transpose, out_f32):
+    """mauv_resize_u8 with the move applied where the last pass stores: into uint8
+    [B, Ho, Wo, C] (out_u8) or through the staging maths into fp32 [B, C, Ho, Wo] (out_f32)."""
+    _dev(torch.uint8, x, workspace, out_u8)
+    B, H, W, C = x.shape
+    _dev(torch.float32, out_f32)
+    need = int(lib.mauv_resize_workspace_bytes(B, H, W, C, Ho, Wo))
+    if need < 0 or workspace.numel() < need:
+        raise ValueError(f"resize_u8_aug: workspace smaller than resize_workspace_bytes = {need}")
+    for o in (out_u8, out_f32):
+        if o is not None and o.numel() != B * Ho * Wo * C:
+            raise ValueError("the output must hold B * Ho * Wo * C elements")
+    _aug_operands(B, C, Ho * Wo, ops_, turb, dist, (mean, std, beta, binf))
+    check(lib.mauv_resize_u8_aug(_p(x), B, H, W, C, Ho, Wo, _p(workspace), _p(out_u8), _p(mean),
+                                 _p(std), _p(beta), _p(binf), _p(dist), depth, _p(ops_), _p(turb),
+                                 int(bool(allow_transpose)), _p(out_f32), stream()),
+          "resize_u8_aug")
+
+
+def stage_f32_aug(x, beta, binf, dist, depth, ops_, turb, allow_transpose, out):
+    """fp32 [B, C, H, W] -> fp32 [B, C, H, W]: the per-item move ``ops_`` (a gather, so ``out``
+    is another tensor), with the UIFM degradation when ``beta`` is given."""
+    _f32(x, out)
+    B, C, H, W = x.shape
+    if out.numel() != x.numel():
+        raise ValueError("out must have x's element count")
+    _aug_operands(B, C, H * W, ops_, turb, dist, (beta, binf))
+    check(lib.mauv_stage_f32_aug(_p(x), B, C, H, W, _p(beta), _p(binf), _p(dist), depth, _p(ops_),
+                                 _p(turb), int(bool(allow_transpose)), _p(out), stream()),
+          "stage_f32_aug")

@@ -154,3 +154,76 @@ def stage_tile_batch(t, optical):
     if optical:
         return resize_to_tensor(t, TILE_SIZE, OPTICAL_MEAN, OPTICAL_STD)
     return resize_to_tensor(t, TILE_SIZE)
+
+
+# ------------------------------------------------------------------ augmented staging (augment.py)
+_consts = {}
+
+
+def _const(vals, dev):
+    """A small fp32 device constant (mean, std, beta, B_inf), copied to a device once."""
+    key = (tuple(vals), dev)
+    t = _consts.get(key)
+    if t is None:
+        t = _consts[key] = _f32_dev(vals, dev)
+    return t
+
+
+def _uifm_consts(C, dev):
+    if C != len(UIFM_BETA):
+        raise ValueError(f"UIFM degradation is defined for {len(UIFM_BETA)}-channel images "
+                         f"(got {C}), as in the reference (beta.view(1, C, 1, 1))")
+    return _const(UIFM_BETA, dev), _const(UIFM_BINF, dev)
+
+
+def resize_to_tensor_aug(tiles, move_ops, turb=None, allow_transpose=False, size=TILE_SIZE,
+                         mean=None, std=None, depth=1.0, dist=None):
+    """:func:`resize_to_tensor` with item b moved by the dihedral code ``move_ops[b]`` (uint8
+    [B] on the device, None = no move) where the last pass stores, and — with ``turb`` (fp32
+    [B]) — degraded with its own turbidity ``turb[b]`` at ``depth``: one pass, as without."""
+    if tiles.dtype != torch.uint8 or tiles.dim() != 4:
+        raise ValueError("tiles must be uint8 [B, H, W, C]")
+    if not tiles.is_cuda:
+        raise ValueError("tiles must be on a ROCm device")
+    tiles = tiles.contiguous()
+    B, H, W, C = tiles.shape
+    Ho, Wo = (size, size) if isinstance(size, int) else size
+    if allow_transpose and Ho != Wo:
+        raise ValueError(f"a transposing move needs a square output, got {(Ho, Wo)}")
+    dev = tiles.device
+    nws = int(lib.mauv_resize_workspace_bytes(B, H, W, C, Ho, Wo))
+    if nws < 0:
+        raise ValueError(f"resize: unsupported shape {tuple(tiles.shape)} -> {(Ho, Wo)}")
+    ws = torch.empty(max(nws, 1), dtype=torch.uint8, device=dev)
+    out = torch.empty(B, C, Ho, Wo, device=dev)
+    m = s = beta = binf = None
+    if mean is not None:
+        m, s = _const(mean, dev), _const(std, dev)
+    if turb is not None:
+        beta, binf = _uifm_consts(C, dev)
+        dist = _dist(dist, B, Ho, Wo, dev)
+    else:
+        dist = None
+    ops.resize_u8_aug(tiles, Ho, Wo, ws, None, m, s, beta, binf, dist, float(depth), move_ops,
+                      turb, allow_transpose, out)
+    return out
+
+
+def stage_f32_aug(x, move_ops, turb=None, allow_transpose=False, depth=1.0, dist=None):
+    """fp32 NCHW tensors the host datasets already transformed: item b moved by ``move_ops[b]``
+    and, with ``turb``, degraded with turbidity ``turb[b]`` in the same (single) pass."""
+    if x.dtype != torch.float32 or x.dim() != 4 or not x.is_cuda:
+        raise ValueError("x must be fp32 [B, C, H, W] on a ROCm device")
+    x = x.contiguous()
+    B, C, H, W = x.shape
+    if allow_transpose and H != W:
+        raise ValueError(f"a transposing move needs a square tile, got {(H, W)}")
+    beta = binf = None
+    if turb is not None:
+        beta, binf = _uifm_consts(C, x.device)
+        dist = _dist(dist, B, H, W, x.device)
+    else:
+        dist = None
+    out = torch.empty_like(x)
+    ops.stage_f32_aug(x, beta, binf, dist, float(depth), move_ops, turb, allow_transpose, out)
+    return out
