@@ -410,6 +410,50 @@ int mauv_accum_note(MauvStepGate* gate, MauvAccum* acc, hipStream_t stream);
 int mauv_adam_step_ex_accum(const MauvAdamEntryEx* table, int n, const MauvAdamGroup* groups,
                             int n_groups, MauvStepGate* gate, MauvLossScale* scaler,
                             MauvAccum* acc, hipStream_t stream);
+/* An exponential moving average (EMA) of the weights decided on the device: every parameter has a
+ * shadow tensor that moves towards it after each Adam step that happened, and only then.  32-byte
+ * device struct beside the gate, as MauvLossScale and MauvAccum; the caller zero-initialises it
+ * and sets decay and warmup (and may set updates when it resumes a run). */
+typedef struct MauvEma {
+  float decay;     /* 0 < decay < 1                                            (caller)  */
+  int   warmup;    /* 0: w = 1 - decay; 1: timm's warm-up, below                (caller)  */
+  int   updates;   /* EMA updates taken so far                                  (library) */
+  float weight;    /* the w of the last update; 1 = "copy"                      (library) */
+  int   reserved[4];
+} MauvEma;
+/* mauv_adam_step_ex_accum with a weight EMA.  ema_rows is a DEVICE array of n float pointers, the
+ * shadow tensor of each table row (row[i].numel floats), NULL for a row without one; ema is the
+ * device MauvEma.  ema == NULL or ema_rows == NULL: exactly mauv_adam_step_ex_accum(table, n,
+ * groups, n_groups, gate, scaler, acc, stream).  Otherwise one thread takes that entry's decision
+ * (scaler and acc may each be NULL, as there) and then, if and only if the decision is "Adam step"
+ * (mode bit 1), with n = updates and d = decay:
+ *   n == 0    -> w = 1 (the first update copies, as torch.optim.swa_utils.AveragedModel)
+ *   otherwise -> with warmup, d = min((double)decay, (1.0 + n) / (10.0 + n)); w = (float)(1.0 - d)
+ * and weight = w, updates = n + 1.  Every other decision (a skip on the loss, non-finite gradients,
+ * a poisoned arena, an overflow, a dropped window) leaves the MauvEma untouched, as does
+ * mauv_accum_note.  The Adam kernel, having formed the new p of a row with a shadow, stores
+ * e = p when w == 1, else e = fmaf(w, p - e, e) (torch's lerp for weights below 0.5) beside it:
+ * one more read and write per element, no extra pass.  A step that does not update never touches
+ * a shadow.  A row takes the loop (16-byte vectors or scalars) it takes without a shadow; a
+ * shadow that is not 16-byte aligned is read and written float by float inside the vector loop,
+ * so p, m, v and the zeroed gradients are mauv_adam_step_ex_accum's bits whatever its address.  Argument errors (a null table / groups
+ * / gate, n outside 1..65535, n_groups outside 1..8) return a negative code before any launch. */
+int mauv_adam_step_ex_ema(const MauvAdamEntryEx* table, int n, const MauvAdamGroup* groups,
+                          int n_groups, MauvStepGate* gate, MauvLossScale* scaler, MauvAccum* acc,
+                          float* const* ema_rows, MauvEma* ema, hipStream_t stream);
+/* The same element update at a host-given weight w (0 < w <= 1; 1 copies), for steps the host
+ * decided, and the element-wise exchange of parameters and shadows in place (no pointer changes:
+ * cached tables stay valid), both over a DEVICE table of n rows in one launch with the Adam
+ * kernels' grid; a row takes 16-byte vectors when both its pointers are 16-byte aligned.  Argument
+ * errors (a null table, n outside 1..65535, w outside (0, 1]) return a negative code before any
+ * launch. */
+typedef struct MauvEmaRow {
+  float* ema;
+  const float* param;   /* written by mauv_ema_swap only */
+  long long numel;
+} MauvEmaRow;
+int mauv_ema_update(const MauvEmaRow* rows, int n, float w, hipStream_t stream);
+int mauv_ema_swap(const MauvEmaRow* rows, int n, hipStream_t stream);
 
 /* ---- global gradient norm + non-finite scan, in-place clip (gradnorm.hip) -------------------
  * torch.nn.utils.clip_grad_norm_ over a DEVICE table of fp32 spans: the flat gradient arena is

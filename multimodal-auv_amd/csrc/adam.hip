@@ -17,6 +17,11 @@
 // mauv_accum_note / mauv_adam_step_ex_accum add gradient accumulation: a window
 // of micro-batches is counted in a MauvAccum beside the gate, the closing call takes the same
 // decision once per window and the kernel multiplies g by 1 / micro between the two factors.
+// mauv_adam_step_ex_ema adds an exponential moving average of the weights: the
+// same decision also forms the average's weight in a MauvEma beside the gate when, and only when,
+// it is "Adam step", and the kernel moves each row's shadow tensor towards the new p it holds in a
+// register.  mauv_ema_update / mauv_ema_swap are the same element update at a host-given weight
+// and the in-place exchange of parameters and shadows.
 #include "mauv_common.h"
 
 using namespace mauv;
@@ -233,8 +238,8 @@ __global__ void accum_note_kernel(MauvStepGate* g, MauvAccum* a) {
 
 // The closing micro-batch (one thread): folded in as above, then the decision of the kernels
 // above once for the window, "loss ok" being "no micro-batch of it had a non-finite loss".
-__global__ void step_gate_accum_kernel(MauvStepGate* g, MauvLossScale* s, MauvAccum* a, float lr,
-                                       float beta1, float beta2) {
+__device__ __forceinline__ void accum_close(MauvStepGate* g, MauvLossScale* s, MauvAccum* a,
+                                            float lr, float beta1, float beta2) {
   const int bad_now = g->ok_loss == 0;
   const int micro = a->micro + 1, bad = a->bad_loss + bad_now;
   const float avg = (float)(1.0 / (double)micro);
@@ -245,6 +250,47 @@ __global__ void step_gate_accum_kernel(MauvStepGate* g, MauvLossScale* s, MauvAc
   a->dropped += bad != 0;
   a->micro = 0;
   a->bad_loss = 0;
+}
+
+__global__ void step_gate_accum_kernel(MauvStepGate* g, MauvLossScale* s, MauvAccum* a, float lr,
+                                       float beta1, float beta2) {
+  accum_close(g, s, a, lr, beta1, beta2);
+}
+
+// ---- weight EMA ------------------------------------------------------------
+// The decision of the kernels above (window, scaler or neither), then, on the same thread and
+// only when it is "Adam step" (mode bit 1), the weight of this update: 1 for the first one
+// (torch's AveragedModel copies), else 1 - decay, the decay capped at (1 + n) / (10 + n) under
+// timm's warm-up.  Every other decision leaves the MauvEma as it is.
+__global__ void step_gate_ema_kernel(MauvStepGate* g, MauvLossScale* s, MauvAccum* a, MauvEma* e,
+                                     float lr, float beta1, float beta2) {
+  if (a) accum_close(g, s, a, lr, beta1, beta2);
+  else if (s) gate_decide_scaled(g, s, g->ok_loss != 0, 1, 1.0f, lr, beta1, beta2);
+  else gate_decide(g, g->ok_loss != 0, 1, 1.0f, lr, beta1, beta2);
+  if (!(g->mode & 1)) return;
+  const int n = e->updates;
+  float w = 1.0f;
+  if (n != 0) {
+    double d = (double)e->decay;
+    if (e->warmup) d = fmin(d, (1.0 + (double)n) / (10.0 + (double)n));
+    w = (float)(1.0 - d);
+  }
+  e->weight = w;
+  e->updates = n + 1;
+}
+
+// The new p as the average reads it: the value the Adam update has settled on, opaque to the
+// compiler, so that the update's own arithmetic (which products it fuses) is compiled exactly as
+// in the instantiations without an average and p keeps their bits.
+__device__ __forceinline__ float settled(float p) {
+  asm volatile("" : "+v"(p));
+  return p;
+}
+
+// One element of the average: torch's lerp for weights below 0.5, e + w (p - e) with the product
+// and the sum in one rounding; w == 1 copies (exact also where p - e would overflow).
+__device__ __forceinline__ float ema_elem(float e, float p, float w) {
+  return w == 1.0f ? p : __builtin_fmaf(w, p - e, e);
 }
 
 // ---- every option, several parameter groups (mauv_adam_step_ex) ------------------------------
@@ -299,10 +345,16 @@ __device__ __forceinline__ void adam_elem_ex(float& p, float g, float& m, float&
   p = p - k.step_size * (m / (sqrtf(d) / k.bc2_sqrt + k.eps));
 }
 
-// The loops of adam_kernel for one row, with a fifth tensor when AMS.
-template <bool AMS, bool MAXI, bool DEC>
+// The loops of adam_kernel for one row, with a fifth tensor when AMS.  EMA: the row's shadow
+// tensor `sh` moves towards the new p at weight w, read and written beside p (only on an
+// updating step: a shadow is never touched otherwise).  sh16: the shadow is 16-byte aligned;
+// one that is not is read and written float by float inside the vector loop, because the two
+// loops of the Adam update do not round alike (the compiler fuses their products differently):
+// a row must not change loops, and with them the bits of p, m and v, over its shadow's address.
+template <bool AMS, bool MAXI, bool DEC, bool EMA>
 __device__ __forceinline__ void adam_row(const MauvAdamEntryEx& t, long long n4, bool upd,
-                                         bool zero, const AdamConsts& k) {
+                                         bool zero, const AdamConsts& k, float* sh = nullptr,
+                                         float w = 1.0f, bool sh16 = true) {
   float* grad = const_cast<float*>(t.grad);
   for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
     if (upd) {
@@ -312,16 +364,29 @@ __device__ __forceinline__ void adam_row(const MauvAdamEntryEx& t, long long n4,
       floatx4 v = ((const floatx4*)t.exp_avg_sq)[i];
       floatx4 x = floatx4{0.f, 0.f, 0.f, 0.f};
       if (AMS) x = ((const floatx4*)t.max_exp_avg_sq)[i];
+      floatx4 s = floatx4{0.f, 0.f, 0.f, 0.f};
+      if (EMA) {
+        if (sh16) s = ((const floatx4*)sh)[i];
+        else s = floatx4{sh[4 * i], sh[4 * i + 1], sh[4 * i + 2], sh[4 * i + 3]};
+      }
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float pe = p[e], me = m[e], ve = v[e], xe = x[e];
         adam_elem_ex<AMS, MAXI, DEC>(pe, g[e], me, ve, xe, k);
         p[e] = pe; m[e] = me; v[e] = ve; x[e] = xe;
+        if (EMA) s[e] = ema_elem(s[e], settled(pe), w);
       }
       ((floatx4*)t.param)[i] = p;
       ((floatx4*)t.exp_avg)[i] = m;
       ((floatx4*)t.exp_avg_sq)[i] = v;
       if (AMS) ((floatx4*)t.max_exp_avg_sq)[i] = x;
+      if (EMA) {
+        if (sh16) {
+          ((floatx4*)sh)[i] = s;
+        } else {
+          sh[4 * i] = s[0]; sh[4 * i + 1] = s[1]; sh[4 * i + 2] = s[2]; sh[4 * i + 3] = s[3];
+        }
+      }
     }
     if (zero) ((floatx4*)grad)[i] = floatx4{0.f, 0.f, 0.f, 0.f};
   }
@@ -337,19 +402,42 @@ __device__ __forceinline__ void adam_row(const MauvAdamEntryEx& t, long long n4,
       t.exp_avg[i] = m;
       t.exp_avg_sq[i] = v;
       if (AMS) t.max_exp_avg_sq[i] = x;
+      if (EMA) sh[i] = ema_elem(sh[i], settled(p), w);
     }
     if (zero) grad[i] = 0.f;
   }
 }
 
+// The row's loops for its group's option flags (uniform over the block).
+template <bool EMA>
+__device__ __forceinline__ void adam_row_flags(unsigned flags, const MauvAdamEntryEx& t,
+                                               long long n4, bool upd, bool zero,
+                                               const AdamConsts& k, float* sh = nullptr,
+                                               float w = 1.0f, bool sh16 = true) {
+  switch (flags) {
+    case 0: adam_row<false, false, false, EMA>(t, n4, upd, zero, k, sh, w, sh16); break;
+    case 1: adam_row<true, false, false, EMA>(t, n4, upd, zero, k, sh, w, sh16); break;
+    case 2: adam_row<false, true, false, EMA>(t, n4, upd, zero, k, sh, w, sh16); break;
+    case 3: adam_row<true, true, false, EMA>(t, n4, upd, zero, k, sh, w, sh16); break;
+    case 4: adam_row<false, false, true, EMA>(t, n4, upd, zero, k, sh, w, sh16); break;
+    case 5: adam_row<true, false, true, EMA>(t, n4, upd, zero, k, sh, w, sh16); break;
+    case 6: adam_row<false, true, true, EMA>(t, n4, upd, zero, k, sh, w, sh16); break;
+    default: adam_row<true, true, true, EMA>(t, n4, upd, zero, k, sh, w, sh16); break;
+  }
+}
+
 // grid.y = table row, as adam_kernel; the row's group gives the constants and the options,
-// which are uniform over the block: one branch per block, outside the element loops.
-template <bool GATED>
+// which are uniform over the block: one branch per block, outside the element loops.  EMA (gated
+// only): ema_rows[row] is the row's shadow tensor or NULL, ema->weight this update's weight; the
+// EMA-off instantiations never look at either.
+template <bool GATED, bool EMA>
 __global__ __launch_bounds__(256) void adam_ex_kernel(const MauvAdamEntryEx* __restrict__ tab,
                                                       AdamGroupsArg ga, int n_groups,
                                                       const MauvStepGate* __restrict__ gate,
                                                       const MauvLossScale* __restrict__ ls,
-                                                      const MauvAccum* __restrict__ acc) {
+                                                      const MauvAccum* __restrict__ acc,
+                                                      float* const* __restrict__ ema_rows,
+                                                      const MauvEma* __restrict__ ema) {
   int mode = 1;
   if (GATED) {
     mode = gate->mode;
@@ -360,6 +448,8 @@ __global__ __launch_bounds__(256) void adam_ex_kernel(const MauvAdamEntryEx* __r
   const int gi = (int)t.group;
   const unsigned flags = ga.g[gi].flags & 7u;
   if ((flags & MAUV_ADAM_AMSGRAD) && !t.max_exp_avg_sq) return;
+  // a shadow is touched by an updating step only
+  float* sh = (EMA && (mode & 1)) ? ema_rows[blockIdx.y] : nullptr;
   // 16-byte vector path only when all (up to five) tensors are 16-byte aligned
   const bool aligned = ((reinterpret_cast<uintptr_t>(t.param) | reinterpret_cast<uintptr_t>(t.grad) |
                          reinterpret_cast<uintptr_t>(t.exp_avg) |
@@ -390,15 +480,46 @@ __global__ __launch_bounds__(256) void adam_ex_kernel(const MauvAdamEntryEx* __r
     k.bc2_sqrt = (float)sqrt(bc2);
   }
   const bool upd = mode & 1, zero = mode & 2;
-  switch (flags) {
-    case 0: adam_row<false, false, false>(t, n4, upd, zero, k); break;
-    case 1: adam_row<true, false, false>(t, n4, upd, zero, k); break;
-    case 2: adam_row<false, true, false>(t, n4, upd, zero, k); break;
-    case 3: adam_row<true, true, false>(t, n4, upd, zero, k); break;
-    case 4: adam_row<false, false, true>(t, n4, upd, zero, k); break;
-    case 5: adam_row<true, false, true>(t, n4, upd, zero, k); break;
-    case 6: adam_row<false, true, true>(t, n4, upd, zero, k); break;
-    default: adam_row<true, true, true>(t, n4, upd, zero, k); break;
+  if (EMA && sh)
+    adam_row_flags<true>(flags, t, n4, upd, zero, k, sh, ema->weight,
+                         (reinterpret_cast<uintptr_t>(sh) & 15) == 0);
+  else adam_row_flags<false>(flags, t, n4, upd, zero, k);
+}
+
+// ---- the average at a host-given weight, and the exchange (mauv_ema_update / mauv_ema_swap) ---
+// grid.y = row, the loops of adam_row: 16-byte vectors when both tensors are 16-byte aligned.
+template <bool SWAP>
+__global__ __launch_bounds__(256) void ema_rows_kernel(const MauvEmaRow* __restrict__ rows,
+                                                       float w) {
+  const MauvEmaRow t = rows[blockIdx.y];
+  if (!t.ema || !t.param) return;
+  float* par = const_cast<float*>(t.param);
+  const bool aligned = ((reinterpret_cast<uintptr_t>(t.ema) |
+                         reinterpret_cast<uintptr_t>(t.param)) & 15) == 0;
+  const long long n4 = aligned ? t.numel / 4 : 0;
+  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+    const floatx4 p = ((const floatx4*)t.param)[i];
+    floatx4 s = ((const floatx4*)t.ema)[i];
+    if (SWAP) {
+      ((floatx4*)par)[i] = s;
+      s = p;
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) s[e] = ema_elem(s[e], p[e], w);
+    }
+    ((floatx4*)t.ema)[i] = s;
+  }
+  // scalar tail
+  const long long base = n4 * 4;
+  for (long long i = base + blockIdx.x * 256LL + threadIdx.x; i < t.numel;
+       i += (long long)gridDim.x * 256) {
+    const float p = t.param[i], s = t.ema[i];
+    if (SWAP) {
+      par[i] = s;
+      t.ema[i] = p;
+    } else {
+      t.ema[i] = ema_elem(s, p, w);
+    }
   }
 }
 
@@ -457,11 +578,11 @@ MAUV_API int mauv_adam_step_ex(const MauvAdamEntryEx* table, int n, const MauvAd
   if (gate) {
     hipLaunchKernelGGL(step_gate_kernel, dim3(1), dim3(1), 0, stream, gate, groups[0].lr,
                        groups[0].beta1, groups[0].beta2);
-    hipLaunchKernelGGL(adam_ex_kernel<true>, dim3(64, n), dim3(256), 0, stream, table, ga,
-                       n_groups, (const MauvStepGate*)gate, nullptr, nullptr);
+    hipLaunchKernelGGL((adam_ex_kernel<true, false>), dim3(64, n), dim3(256), 0, stream, table, ga,
+                       n_groups, (const MauvStepGate*)gate, nullptr, nullptr, nullptr, nullptr);
   } else {
-    hipLaunchKernelGGL(adam_ex_kernel<false>, dim3(64, n), dim3(256), 0, stream, table, ga,
-                       n_groups, nullptr, nullptr, nullptr);
+    hipLaunchKernelGGL((adam_ex_kernel<false, false>), dim3(64, n), dim3(256), 0, stream, table, ga,
+                       n_groups, nullptr, nullptr, nullptr, nullptr, nullptr);
   }
   return check_launch("adam_step_ex");
 }
@@ -491,8 +612,9 @@ MAUV_API int mauv_adam_step_ex_scaled(const MauvAdamEntryEx* table, int n,
   }
   hipLaunchKernelGGL(step_gate_scaled_kernel, dim3(1), dim3(1), 0, stream, gate, scaler,
                      groups[0].lr, groups[0].beta1, groups[0].beta2);
-  hipLaunchKernelGGL(adam_ex_kernel<true>, dim3(64, n), dim3(256), 0, stream, table, ga,
-                     n_groups, (const MauvStepGate*)gate, (const MauvLossScale*)scaler, nullptr);
+  hipLaunchKernelGGL((adam_ex_kernel<true, false>), dim3(64, n), dim3(256), 0, stream, table, ga,
+                     n_groups, (const MauvStepGate*)gate, (const MauvLossScale*)scaler, nullptr,
+                     nullptr, nullptr);
   return check_launch("adam_step_ex_scaled");
 }
 
@@ -529,8 +651,57 @@ MAUV_API int mauv_adam_step_ex_accum(const MauvAdamEntryEx* table, int n,
   }
   hipLaunchKernelGGL(step_gate_accum_kernel, dim3(1), dim3(1), 0, stream, gate, scaler, acc,
                      groups[0].lr, groups[0].beta1, groups[0].beta2);
-  hipLaunchKernelGGL(adam_ex_kernel<true>, dim3(64, n), dim3(256), 0, stream, table, ga,
+  hipLaunchKernelGGL((adam_ex_kernel<true, false>), dim3(64, n), dim3(256), 0, stream, table, ga,
                      n_groups, (const MauvStepGate*)gate, (const MauvLossScale*)scaler,
-                     (const MauvAccum*)acc);
+                     (const MauvAccum*)acc, nullptr, nullptr);
   return check_launch("adam_step_ex_accum");
+}
+
+// The gated step with a weight EMA (mauv.h): the decision of mauv_adam_step_ex_accum (scaler and
+// acc may each be NULL) also forms the average's weight, then the Adam launch moves every row's
+// shadow.  ema == NULL or ema_rows == NULL is exactly mauv_adam_step_ex_accum(table, n, groups,
+// n_groups, gate, scaler, acc, stream).
+MAUV_API int mauv_adam_step_ex_ema(const MauvAdamEntryEx* table, int n,
+                                   const MauvAdamGroup* groups, int n_groups, MauvStepGate* gate,
+                                   MauvLossScale* scaler, MauvAccum* acc, float* const* ema_rows,
+                                   MauvEma* ema, hipStream_t stream) {
+  if (n <= 0 || n > 65535 || !table) {
+    set_error("adam_step_ex_ema: bad table size");
+    return kErrArg;
+  }
+  if (n_groups < 1 || n_groups > MAUV_ADAM_MAX_GROUPS || !groups) {
+    set_error("adam_step_ex_ema: 1..8 parameter groups");
+    return kErrArg;
+  }
+  if (!gate) { set_error("adam_step_ex_ema: no gate"); return kErrArg; }
+  if (!ema || !ema_rows)
+    return mauv_adam_step_ex_accum(table, n, groups, n_groups, gate, scaler, acc, stream);
+  AdamGroupsArg ga = {};
+  for (int i = 0; i < n_groups; ++i) {
+    ga.g[i] = groups[i];
+    ga.step_size[i] = 0.f;
+    ga.bc2_sqrt[i] = 1.f;
+  }
+  hipLaunchKernelGGL(step_gate_ema_kernel, dim3(1), dim3(1), 0, stream, gate, scaler, acc, ema,
+                     groups[0].lr, groups[0].beta1, groups[0].beta2);
+  hipLaunchKernelGGL((adam_ex_kernel<true, true>), dim3(64, n), dim3(256), 0, stream, table, ga,
+                     n_groups, (const MauvStepGate*)gate, (const MauvLossScale*)scaler,
+                     (const MauvAccum*)acc, ema_rows, (const MauvEma*)ema);
+  return check_launch("adam_step_ex_ema");
+}
+
+// The average's element update at a host-given weight over a device table of (shadow, parameter,
+// numel) rows (mauv.h): for steps the host decided.  w == 1 copies.
+MAUV_API int mauv_ema_update(const MauvEmaRow* rows, int n, float w, hipStream_t stream) {
+  if (n <= 0 || n > 65535 || !rows) { set_error("ema_update: bad table size"); return kErrArg; }
+  if (!(w > 0.f && w <= 1.f)) { set_error("ema_update: weight outside (0, 1]"); return kErrArg; }
+  hipLaunchKernelGGL(ema_rows_kernel<false>, dim3(64, n), dim3(256), 0, stream, rows, w);
+  return check_launch("ema_update");
+}
+
+// Parameters and shadows exchanged element-wise, in place (mauv.h): no pointer changes.
+MAUV_API int mauv_ema_swap(const MauvEmaRow* rows, int n, hipStream_t stream) {
+  if (n <= 0 || n > 65535 || !rows) { set_error("ema_swap: bad table size"); return kErrArg; }
+  hipLaunchKernelGGL(ema_rows_kernel<true>, dim3(64, n), dim3(256), 0, stream, rows, 1.0f);
+  return check_launch("ema_swap");
 }

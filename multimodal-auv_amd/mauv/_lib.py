@@ -57,6 +57,9 @@ SIGNATURES = {
     "mauv_adam_step_ex_scaled": [P, I, P, I, P, P, P],
     "mauv_accum_note": [P, P, P],
     "mauv_adam_step_ex_accum": [P, I, P, I, P, P, P, P],
+    "mauv_adam_step_ex_ema": [P, I, P, I, P, P, P, P, P, P],
+    "mauv_ema_update": [P, I, F, P],
+    "mauv_ema_swap": [P, I, P],
     # gradnorm.hip
     "mauv_grad_norm_workspace_bytes": [I],
     "mauv_grad_norm": [P, I, I, P, P, P, P],
@@ -152,6 +155,16 @@ class MauvAccum(ctypes.Structure):
     """include/mauv.h MauvAccum: the device state of a gradient-accumulation window (32 bytes)."""
     _fields_ = [("micro", I), ("bad_loss", I), ("avg", F), ("windows", I), ("dropped", I),
                 ("reserved", I * 3)]
+
+
+class MauvEma(ctypes.Structure):
+    """include/mauv.h MauvEma: the device state of the weight EMA (32 bytes)."""
+    _fields_ = [("decay", F), ("warmup", I), ("updates", I), ("weight", F), ("reserved", I * 4)]
+
+
+class MauvEmaRow(ctypes.Structure):
+    """include/mauv.h MauvEmaRow: one (shadow, parameter, numel) row of mauv_ema_update / _swap."""
+    _fields_ = [("ema", P), ("param", P), ("numel", LL)]
 
 
 class MauvError(RuntimeError):

@@ -13,11 +13,18 @@
                                             FusedAdam's device scaler, or for a host model a
                                             torch.amp.GradScaler("cpu") hung on the optimizer;
                                             grad_accumulation (an integer >= 1) turns gradient
-                                            accumulation on for either optimizer)
+                                            accumulation on for either optimizer;
+                                            ema_decay / ema_warmup / ema_eval turn the weight
+                                            EMA on: FusedAdam's own, or for a host model a
+                                            mauv.optim.HostEma hung on the optimizer)
 * ``train_and_evaluate_unimodal_model``     loop_utils.py:65-159 (epochs ``range(1, n)``)
 * ``train_and_evaluate_multimodal_model``   loop_utils.py:162-250 (scheduler stepped after
                                             training AND after evaluation, as the reference)
+
+When the optimizer carries a weight EMA and its ``ema_eval`` is true, both loops run the
+evaluation call inside ``averaged()``: on the averaged weights, the live ones back afterwards.
 """
+import contextlib
 import logging
 import os
 
@@ -25,8 +32,8 @@ import torch.nn as nn
 import torch.optim as optim
 
 from .amp import host_grad_scaler, own_loss_scaler
-from .optim import (FusedAdam, check_max_grad_norm, check_grad_norm_type,
-                    check_grad_accumulation)
+from .optim import (FusedAdam, HostEma, ema_of, check_max_grad_norm, check_grad_norm_type,
+                    check_grad_accumulation, check_ema_decay)
 from .train import (train_unimodal_model, evaluate_unimodal_model, train_multimodal_model,
                     evaluate_multimodal_model)
 
@@ -52,15 +59,25 @@ def define_optimizers_and_schedulers(models_dict, optimizer_params=None, schedul
         kind = check_grad_norm_type(kw.pop("grad_norm_type", 2.0))
         scaler = host_grad_scaler(kw.pop("loss_scale", None))
         accumulation = check_grad_accumulation(kw.pop("grad_accumulation", None))
+        decay = check_ema_decay(kw.pop("ema_decay", None))
+        ema_kw = {k: kw.pop(k) for k in ("ema_warmup", "ema_eval") if k in kw}
         opt = optim.Adam(params, **kw)
         opt.max_grad_norm, opt.grad_norm_type = clip, kind
         opt.grad_scaler = scaler
         opt.grad_accumulation = accumulation
+        opt.ema = None if decay is None else HostEma(params, decay, **ema_kw)
         return opt
     optimizers = {k: adam(models_dict[k], optimizer_params[k]) for k in _MODEL_KEYS}
     schedulers = {k: optim.lr_scheduler.StepLR(optimizers[k], **scheduler_params[k])
                   for k in optimizers}
     return criterion, optimizers, schedulers
+
+
+def _evaluation_weights(optimizer):
+    """The context the evaluation call runs in: the optimizer's ``averaged()`` when it carries
+    a weight EMA with ``ema_eval`` true, else nothing."""
+    ema = ema_of(optimizer)
+    return ema.averaged() if ema is not None and ema.ema_eval else contextlib.nullcontext()
 
 
 def train_and_evaluate_unimodal_model(model, train_loader, test_loader, criterion, optimizer,
@@ -74,10 +91,11 @@ def train_and_evaluate_unimodal_model(model, train_loader, test_loader, criterio
             epoch=epoch, total_num_epochs=num_epochs, num_mc=num_mc, device=device,
             model_type=model_name, csv_path=os.path.join(save_dir, f"{model_name}.csv"),
             sum_writer=sum_writer)
-        val_accuracy = evaluate_unimodal_model(
-            model=model, dataloader=test_loader, device=device, epoch=epoch,
-            total_num_epochs=num_epochs, num_mc=num_mc, model_type=model_name,
-            csv_path=os.path.join(save_dir, f"{model_name}_evaluate.csv"))
+        with _evaluation_weights(optimizer):
+            val_accuracy = evaluate_unimodal_model(
+                model=model, dataloader=test_loader, device=device, epoch=epoch,
+                total_num_epochs=num_epochs, num_mc=num_mc, model_type=model_name,
+                csv_path=os.path.join(save_dir, f"{model_name}_evaluate.csv"))
         scheduler.step()
         sum_writer.add_scalar("train/loss/epoch", train_loss, epoch)
         sum_writer.add_scalar("val/accuracy/epoch", val_accuracy, epoch)
@@ -102,12 +120,13 @@ def train_and_evaluate_multimodal_model(train_loader, test_loader, multimodal_mo
             sss_patch_type=sss_patch_type,
             csv_path=os.path.join(csv_path, "multimodal_training.csv"), sum_writer=sum_writer)
         lr_scheduler.step()
-        val_accuracy = evaluate_multimodal_model(
-            multimodal_model=multimodal_model, dataloader=test_loader, device=device,
-            epoch=epoch, total_num_epochs=num_epochs, num_mc=num_mc,
-            csv_path=os.path.join(csv_path, "multimodal_test.csv"),
-            bathy_patch_type=bathy_patch_type, sss_patch_type=sss_patch_type,
-            model_type=model_type)
+        with _evaluation_weights(optimizer):
+            val_accuracy = evaluate_multimodal_model(
+                multimodal_model=multimodal_model, dataloader=test_loader, device=device,
+                epoch=epoch, total_num_epochs=num_epochs, num_mc=num_mc,
+                csv_path=os.path.join(csv_path, "multimodal_test.csv"),
+                bathy_patch_type=bathy_patch_type, sss_patch_type=sss_patch_type,
+                model_type=model_type)
         lr_scheduler.step()
         sum_writer.add_scalar("train/loss/epoch", train_loss, epoch)
         sum_writer.add_scalar("val/accuracy/epoch", val_accuracy, epoch)

@@ -60,7 +60,31 @@ scaler moves once per window, and the kernel multiplies each gradient by 1 / mic
 ``zero_grad()`` also abandons the open window.  The ungated ``step()`` and
 ``mauv.amp.LossScaler.step(opt)`` in a user's own loop do not look at the option: such a loop
 divides its gradients itself.
+
+``ema_decay`` (None, or a number with 0 < d < 1) keeps an exponential moving average (EMA) of the
+weights beside Adam, what ``torch.optim.swa_utils.AveragedModel`` with
+``get_ema_multi_avg_fn(d)`` or timm's ``ModelEma`` keep: after every step that HAPPENED, and only
+then, each parameter's shadow moves towards it, ``e += (1 - d)(p - e)``; the first update copies.
+``ema_warmup=True`` caps the decay at ``(1 + n) / (10 + n)`` on update n (timm's warm-up).
+``ema_eval`` (default True) tells the training loops to evaluate on the averaged weights.  All
+three are plain attributes like ``max_grad_norm``, no ``param_groups`` keys.  The shadow of a
+parameter is ``state[p]["ema"]``, created beside ``exp_avg`` as a clone of the parameter (frozen
+parameters get none; with the option off the key never appears), so ``state_dict()`` carries the
+shadows, and beside them a top-level ``"ema_updates"``; it still loads into torch.optim.Adam and
+back.  The gated form takes the all-groups entry ``mauv_adam_step_ex_ema``: the device decision
+also forms the weight, in a ``MauvEma`` beside the gate, and the Adam kernel stores the shadow
+beside the new parameter it holds in a register — no extra pass and no host wait; a skipped step
+(bad loss, non-finite gradients, overflow, dropped window) moves nothing.  The ungated ``step()``
+is decided on the host: its Adam launches are followed by ``mauv_ema_update`` over the same live
+parameters at the weight of a host count kept equal to the device rule — ONE EXTRA PASS over
+parameters and shadows.  ``step()`` with a loss scaler takes the gated entry, EMA included.
+``swap_ema()`` exchanges parameters and shadows in place (``mauv_ema_swap``; no pointer changes,
+so no cached table or engine state is invalidated), ``averaged()`` is the context manager that
+swaps in and, on exit, back, ``ema_parameters()`` lists ``(p, shadow)``.  While swapped, ``step``,
+``step_gated`` and ``state_dict`` raise RuntimeError.  BatchNorm buffers (running statistics) are
+not averaged — AveragedModel's default: under the swap the live buffers serve.
 """
+import contextlib
 import ctypes
 import math
 import numbers
@@ -78,6 +102,8 @@ G_MAX_NORM, G_GRAD_NORM, G_CLIP_COEF, G_NORM_KIND = 10, 11, 12, 13   # fp32, fp3
 G_SCRATCH = 15           # a reserved word the training step counts non-finite inputs in
 ACC_WORDS = 8            # sizeof(MauvAccum) / 4
 A_MICRO, A_BAD_LOSS, A_AVG, A_WINDOWS, A_DROPPED = range(5)   # int, int, fp32, int, int
+EMA_WORDS = 8            # sizeof(MauvEma) / 4
+E_DECAY, E_WARMUP, E_UPDATES, E_WEIGHT = range(4)             # fp32, int, int, fp32
 MAX_GROUPS = 8           # MAUV_ADAM_MAX_GROUPS
 F_AMSGRAD, F_MAXIMIZE, F_DECOUPLED = 1, 2, 4
 EX = "ex"                # key of the all-groups table / fast entry (group 0 alone keeps key 0)
@@ -111,6 +137,34 @@ def check_grad_accumulation(v):
     if isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < 1:
         raise ValueError(f"grad_accumulation must be None or an integer >= 1, got {v!r}")
     return int(v)
+
+
+def check_ema_decay(v):
+    """``ema_decay``: None (no weight EMA) or a Python number with 0 < d < 1."""
+    if v is None:
+        return None
+    if isinstance(v, bool) or not isinstance(v, numbers.Real) or not 0 < v < 1:
+        raise ValueError(f"ema_decay must be None or a number with 0 < d < 1, got {v!r}")
+    return float(v)
+
+
+def check_ema_flag(name, v):
+    """``ema_warmup`` / ``ema_eval``: a bool."""
+    if not isinstance(v, bool):
+        raise ValueError(f"{name} must be True or False, got {v!r}")
+    return v
+
+
+def ema_weight(n, decay, warmup):
+    """The weight of EMA update number ``n`` (0-based) as the device forms it (adam.hip
+    step_gate_ema_kernel): 1 for the first update, else (float)(1 - d) with d the fp32 decay,
+    capped at (1 + n) / (10 + n) under the warm-up."""
+    if n == 0:
+        return 1.0
+    d = float(np.float32(decay))
+    if warmup:
+        d = min(d, (1.0 + n) / (10.0 + n))
+    return float(np.float32(1.0 - d))
 
 
 def _span_rows(grads):
@@ -157,7 +211,8 @@ class FusedAdam(torch.optim.Optimizer):
                  amsgrad=False, *, foreach=None, maximize=False, capturable=False,
                  differentiable=False, fused=None, decoupled_weight_decay=False,
                  max_grad_norm=None, grad_norm_type=2.0, loss_scale=None,
-                 grad_accumulation=None, **unsupported):
+                 grad_accumulation=None, ema_decay=None, ema_warmup=False, ema_eval=True,
+                 **unsupported):
         for k, v in unsupported.items():
             if v not in (None, False):
                 raise ValueError(f"FusedAdam: unsupported option {k}={v}")
@@ -175,6 +230,17 @@ class FusedAdam(torch.optim.Optimizer):
         self.grad_accumulation = grad_accumulation
         self._accum = None         # device MauvAccum (int32[8]) beside the gate
         self._accum_micro = 0      # micro-batches of the open window (host count)
+        # weight EMA: plain attributes too; the shadows live in the per-parameter state
+        self.ema_decay = ema_decay
+        self.ema_warmup = ema_warmup
+        self.ema_eval = ema_eval
+        self._ema = None           # device MauvEma (int32[8]) beside the gate
+        self._ema_opts = None      # (decay, warmup) the device struct holds
+        self._ema_updates = 0      # EMA updates taken (host count; see _ema_dirty)
+        self._ema_dirty = False    # the device count is ahead of the host count (gated steps)
+        self._ema_pushed = False   # the device count holds the host count (or is ahead of it)
+        self._ema_rows = None      # (key, device MauvEmaRow table) of mauv_ema_update / _swap
+        self._ema_swapped = False  # swap_ema(): the parameters hold the averages right now
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
                                       amsgrad=amsgrad, maximize=maximize, foreach=foreach,
                                       capturable=capturable, differentiable=differentiable,
@@ -224,6 +290,30 @@ class FusedAdam(torch.optim.Optimizer):
     @grad_accumulation.setter
     def grad_accumulation(self, v):
         self.__dict__["_grad_accumulation"] = check_grad_accumulation(v)
+
+    @property
+    def ema_decay(self):
+        return self.__dict__.get("_ema_decay")
+
+    @ema_decay.setter
+    def ema_decay(self, v):
+        self.__dict__["_ema_decay"] = check_ema_decay(v)
+
+    @property
+    def ema_warmup(self):
+        return self.__dict__.get("_ema_warmup", False)
+
+    @ema_warmup.setter
+    def ema_warmup(self, v):
+        self.__dict__["_ema_warmup"] = check_ema_flag("ema_warmup", v)
+
+    @property
+    def ema_eval(self):
+        return self.__dict__.get("_ema_eval", True)
+
+    @ema_eval.setter
+    def ema_eval(self, v):
+        self.__dict__["_ema_eval"] = check_ema_flag("ema_eval", v)
 
     def accumulating(self):
         """Gradient accumulation is on (K > 1), or a window opened under it is still open."""
@@ -361,28 +451,45 @@ class FusedAdam(torch.optim.Optimizer):
                        st["exp_avg_sq"].data_ptr(),
                        st["max_exp_avg_sq"].data_ptr() if ams[gi] else 0, p.numel(),
                        len(chunks[-1][2]) - 1)
-        ident = (rows.tobytes(), tuple((a, b, tuple(c)) for a, b, c in chunks))
+        # with the weight EMA on, the rows' shadow pointers travel in a table of their own
+        sh = None
+        if self.ema_decay is not None:
+            sh = np.array([self.state[p]["ema"].data_ptr() for p, _ in pairs], dtype=np.int64)
+        ident = (rows.tobytes(), tuple((a, b, tuple(c)) for a, b, c in chunks),
+                 None if sh is None else sh.tobytes())
         cached = self._tables.get(key)
         if cached is not None and cached[0] == ident:
             return cached[1]
-        tab = (torch.from_numpy(rows).to(pairs[0][0].device), ident[1])
+        dev = pairs[0][0].device
+        tab = (torch.from_numpy(rows).to(dev), ident[1],
+               None if sh is None else torch.from_numpy(sh).to(dev))
         self._tables[key] = (ident, tab)
         return tab
 
-    def _launch_ex(self, tab, t, gate, scaler=None, accum=None):
+    def _launch_ex(self, tab, t, gate, scaler=None, accum=None, ema=None):
         """mauv_adam_step_ex over every launch of ``tab``; the groups' current lr, betas, eps,
         weight_decay and flags travel by value.  ``scaler``: the device MauvLossScale pointer of
         a gated step with loss scaling (mauv_adam_step_ex_scaled; one launch).  ``accum``: the
         device MauvAccum pointer of a gated step that closes an accumulation window
-        (mauv_adam_step_ex_accum, with or without a scaler; one launch)."""
-        table, chunks = tab
-        assert (scaler is None and accum is None) or (gate is not None and len(chunks) == 1)
+        (mauv_adam_step_ex_accum, with or without a scaler; one launch).  ``ema``: the device
+        MauvEma pointer of a gated step with the weight EMA (mauv_adam_step_ex_ema, with or
+        without either of the others; one launch)."""
+        table, chunks, shadows = tab
+        assert (scaler is None and accum is None and ema is None) or \
+            (gate is not None and len(chunks) == 1)
+        assert ema is None or shadows is not None
         for r0, n, gis in chunks:
             arr = (MauvAdamGroup * len(gis))()
             for a, gi in zip(arr, gis):
                 g = self.param_groups[gi]
                 a.lr, a.eps, a.weight_decay = g["lr"], g["eps"], g["weight_decay"]
                 (a.beta1, a.beta2), a.flags = g["betas"], _flags(g)
+            if ema is not None:
+                check(lib.mauv_adam_step_ex_ema(table.data_ptr() + 56 * r0, n,
+                                                ctypes.addressof(arr), len(gis), gate, scaler,
+                                                accum, shadows.data_ptr() + 8 * r0, ema,
+                                                ops.stream()), "adam_step_ex_ema")
+                continue
             if accum is not None:
                 check(lib.mauv_adam_step_ex_accum(table.data_ptr() + 56 * r0, n,
                                                   ctypes.addressof(arr), len(gis), gate, scaler,
@@ -414,6 +521,12 @@ class FusedAdam(torch.optim.Optimizer):
                     return None
                 if len(mom) == 3 and st["max_exp_avg_sq"] is not mom[2]:
                     return None
+            if len(fast) > 8:   # the shadows the all-groups table points at (None: EMA off)
+                if (fast[8] is None) != (self.ema_decay is None):
+                    return None
+                for p, sh in zip(live, fast[8] or ()):
+                    if self.state[p]["ema"] is not sh:
+                        return None
         except KeyError:
             return None
         return fast
@@ -432,6 +545,9 @@ class FusedAdam(torch.optim.Optimizer):
                 st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
             if group["amsgrad"] and "max_exp_avg_sq" not in st:
                 st["max_exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            if self.ema_decay is not None and "ema" not in st:
+                # the shadow starts from the parameter's current value (also one that joins later)
+                st["ema"] = p.detach().clone(memory_format=torch.preserve_format)
 
     def _remember(self, gi, live, t, tab, layout=None):
         # re-home the step counters as 0-dim views of one CPU tensor (still float tensors,
@@ -446,7 +562,8 @@ class FusedAdam(torch.optim.Optimizer):
                        for p, row_group, mom in zip(live, layout[0], moments)]
         self._fast[gi] = ([p.data_ptr() for p in live], [p.grad.data_ptr() for p in live],
                           moments, id(self.state), t, tab, buf) + \
-            (() if layout is None else (layout,))
+            (() if layout is None else
+             (layout, None if self.ema_decay is None else [self.state[p]["ema"] for p in live]))
 
     def _step_ex(self):
         """The ungated step of anything but one plain group: every group with live parameters
@@ -482,6 +599,7 @@ class FusedAdam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        self._not_swapped("step")
         if self._scaler() is not None:
             self._step_scaled()
             return loss
@@ -491,9 +609,35 @@ class FusedAdam(torch.optim.Optimizer):
             self._clip_live()
         else:
             self.last_grad_norm = None
+        if self.ema_decay is not None:
+            self._step_then_ema()
+            return loss
+        self._step_adam()
+        return loss
+
+    def _step_then_ema(self):
+        """The ungated step with the weight EMA on: the Adam launches as without it, then
+        ``mauv_ema_update`` over the same live parameters, at the weight the device rule gives
+        the host's update count — one extra pass over parameters and shadows."""
+        live = [p for g in self.param_groups for p in g["params"] if p.grad is not None]
+        for p in live:   # a parameter stepped before the option was set: its shadow starts here
+            st = self.state.get(p)
+            if st and "ema" not in st:
+                st["ema"] = p.detach().clone(memory_format=torch.preserve_format)
+        self._step_adam()
+        if not live:
+            return
+        rows = self._ema_row_table([(p, self.state[p]["ema"]) for p in live])
+        w = ema_weight(self._ema_updates, self.ema_decay, self.ema_warmup)
+        check(lib.mauv_ema_update(rows.data_ptr(), len(live), w, ops.stream()), "ema_update")
+        self._ema_updates += 1
+        self._ema_pushed = False
+
+    def _step_adam(self):
+        """The Adam launches of the ungated step."""
         if not self._simple():
             self._step_ex()
-            return loss
+            return
         for gi, group in enumerate(self.param_groups):
             live = [p for p in group["params"] if p.grad is not None]
             if not live:
@@ -524,7 +668,6 @@ class FusedAdam(torch.optim.Optimizer):
                                          ops.stream()), "adam_step")
                 if len(steps) == 1:
                     self._remember(gi, ps, t, tab)
-        return loss
 
     def _step_scaled(self):
         """``step()`` with a loss scaler: the gated step on a gate of this optimizer's own over
@@ -625,6 +768,7 @@ class FusedAdam(torch.optim.Optimizer):
         the all-groups entry.  The ungated ``step()`` and ``mauv.amp.LossScaler.step(opt)`` in
         a user's own loop ignore the option."""
         assert gate is self._gate, "step_gated: use the gate returned by FusedAdam.gate()"
+        self._not_swapped("step_gated")
         accum = None
         if self.accumulating():
             closing = self.closes_window(close)
@@ -657,9 +801,10 @@ class FusedAdam(torch.optim.Optimizer):
         if any(p.grad is None for p in live):
             raise RuntimeError("step_gated: every parameter needs a gradient tensor")
         ls = self._scaler()
-        # with a loss scaler or an accumulation window every layout takes the all-groups entry:
-        # one plain group there is adam_elem, the simple kernel's element
-        simple = self._simple() and ls is None and accum is None
+        ema_on = self.ema_decay is not None
+        # with a loss scaler, an accumulation window or the weight EMA every layout takes the
+        # all-groups entry: one plain group there is adam_elem, the simple kernel's element
+        simple = self._simple() and ls is None and accum is None and not ema_on
         if simple:
             group = self.param_groups[0]
             b1, b2 = group["betas"]
@@ -693,7 +838,9 @@ class FusedAdam(torch.optim.Optimizer):
         else:
             self._launch_ex(tab, 0, gate.data_ptr(),
                             None if ls is None else ls.device_state(gate.device).data_ptr(),
-                            None if accum is None else accum.data_ptr())
+                            None if accum is None else accum.data_ptr(),
+                            self._ema_state(gate.device).data_ptr() if ema_on else None)
+            self._ema_dirty = self._ema_dirty or ema_on
         self.last_grad_norm = None if self.max_grad_norm is None else \
             gate[G_GRAD_NORM:G_GRAD_NORM + 1].view(torch.float32).clone()[0]
         self._gate_dirty = True
@@ -702,9 +849,95 @@ class FusedAdam(torch.optim.Optimizer):
         """Step count held by the gate (one device read; only on a cache rebuild)."""
         return int(self._gate[G_STEP].item()) if self._gate is not None else 0
 
+    # ---- the weight EMA ----------------------------------------------------------------------
+    def _ema_state(self, device):
+        """The device MauvEma of the gated form, holding the current options and an update
+        count that is the host's or ahead of it; device fills only, no host synchronisation."""
+        opts = (self.ema_decay, self.ema_warmup)
+        e = self._ema
+        if e is None or e.device != torch.device(device):
+            self._sync_ema()
+            w = np.zeros(EMA_WORDS, dtype=np.int32)
+            w.view(np.float32)[E_DECAY] = opts[0]
+            w[E_WARMUP], w[E_UPDATES] = opts[1], self._ema_updates
+            e = self._ema = torch.from_numpy(w).to(device)
+            self._ema_opts, self._ema_pushed = opts, True
+        if self._ema_opts != opts:
+            e[E_DECAY:E_DECAY + 1].view(torch.float32).fill_(opts[0])
+            e[E_WARMUP:E_WARMUP + 1].fill_(int(opts[1]))
+            self._ema_opts = opts
+        if not self._ema_pushed:
+            e[E_UPDATES:E_UPDATES + 1].fill_(self._ema_updates)
+            self._ema_pushed = True
+        return e
+
+    def _sync_ema(self):
+        """After gated steps, bring the host's EMA update count up to the device's (one device
+        read, where _sync_gate reads the step count)."""
+        if self._ema is not None and self._ema_dirty:
+            self._ema_updates = int(self._ema[E_UPDATES].item())
+        self._ema_dirty = False
+
+    @property
+    def ema_updates(self):
+        """EMA updates taken so far (after gated steps: one device read)."""
+        self._sync_ema()
+        return self._ema_updates
+
+    def ema_parameters(self):
+        """[(parameter, its shadow)] of every parameter that holds one."""
+        return [(p, self.state[p]["ema"]) for g in self.param_groups for p in g["params"]
+                if "ema" in self.state.get(p, ())]
+
+    def _ema_row_table(self, pairs):
+        """The device MauvEmaRow table over ``pairs``, rebuilt only when a pointer changes."""
+        rows = np.array([(e.data_ptr(), p.data_ptr(), p.numel()) for p, e in pairs],
+                        dtype=np.int64)
+        if len(rows) > 65535:
+            raise ValueError("FusedAdam: more than 65535 tensors with a weight EMA")
+        key = (rows.tobytes(), pairs[0][0].device)
+        if self._ema_rows is None or self._ema_rows[0] != key:
+            self._ema_rows = (key, torch.from_numpy(rows).to(pairs[0][0].device))
+        return self._ema_rows[1]
+
+    def _not_swapped(self, what):
+        if self.__dict__.get("_ema_swapped"):
+            raise RuntimeError(f"FusedAdam.{what}: the parameters hold the averaged weights "
+                               "(swap_ema() / averaged()); swap back first")
+
+    @torch.no_grad()
+    def swap_ema(self):
+        """Exchange every parameter with its shadow, element-wise and in place
+        (``mauv_ema_swap``): the model then computes on the averaged weights, and a second call
+        brings the live ones back bit for bit.  No pointer changes, so cached tables and engine
+        state stay valid.  BatchNorm buffers are not averaged: the live ones serve."""
+        if self.ema_decay is None and not self.ema_parameters():
+            raise RuntimeError("FusedAdam.swap_ema: no weight EMA (ema_decay is None)")
+        pairs = self.ema_parameters()
+        if pairs:
+            for p, e in pairs:
+                if not (p.is_cuda and e.is_cuda and p.is_contiguous() and e.is_contiguous()
+                        and p.dtype == e.dtype == torch.float32):
+                    raise TypeError("FusedAdam: dense contiguous fp32 ROCm parameters only")
+            with torch.cuda.device(pairs[0][0].device):
+                rows = self._ema_row_table(pairs)
+                check(lib.mauv_ema_swap(rows.data_ptr(), len(pairs), ops.stream()), "ema_swap")
+        self._ema_swapped = not self._ema_swapped
+
+    @contextlib.contextmanager
+    def averaged(self):
+        """``with opt.averaged():`` the model runs on the averaged weights (evaluate, save);
+        the live weights are back, bit for bit, on exit."""
+        self.swap_ema()
+        try:
+            yield self
+        finally:
+            self.swap_ema()
+
     def _sync_gate(self):
         """After gated steps, bring state["step"] up to the device count (before an ungated
         step or a state_dict)."""
+        self._sync_ema()
         if self._gate is None or not self._gate_dirty:
             return
         t = self._gate_step_host()
@@ -720,11 +953,20 @@ class FusedAdam(torch.optim.Optimizer):
         self._gate_dirty = False
 
     def state_dict(self):
+        """torch's state_dict; with the weight EMA it carries the shadows (``state[p]["ema"]``)
+        and a top-level ``"ema_updates"``, and still loads into torch.optim.Adam."""
+        self._not_swapped("state_dict")
         self._sync_gate()
-        return super().state_dict()
+        sd = super().state_dict()
+        if self.ema_decay is not None:
+            sd["ema_updates"] = self._ema_updates
+        return sd
 
     def load_state_dict(self, state_dict):
-        """torch's load (new state tensors, step counts): the cached tables are dropped."""
+        """torch's load (new state tensors, step counts): the cached tables are dropped.  A
+        top-level ``"ema_updates"`` restores the EMA update count."""
+        self._not_swapped("load_state_dict")
+        self._sync_ema()
         super().load_state_dict(state_dict)
         for group in self.param_groups:   # a state_dict saved before these keys existed
             for k, v in self.defaults.items():
@@ -734,6 +976,10 @@ class FusedAdam(torch.optim.Optimizer):
         self._fast.clear()
         self._gate = None
         self._gate_dirty = False
+        self._ema_rows = None
+        if "ema_updates" in state_dict:
+            self._ema_updates = int(state_dict["ema_updates"])
+            self._ema_dirty = self._ema_pushed = False
 
 
 class FusedAdamW(FusedAdam):
@@ -746,6 +992,69 @@ class FusedAdamW(FusedAdam):
             raise ValueError("FusedAdamW: decoupled_weight_decay is always on")
         super().__init__(params, lr, betas, eps, weight_decay, amsgrad,
                          decoupled_weight_decay=True, **options)
+
+
+class HostEma:
+    """The weight EMA of a host model under a torch optimizer, FusedAdam's interface on torch's
+    own kernels: define_optimizers_and_schedulers hangs one on the optimizer (``optimizer.ema``)
+    and the training loops call ``update()`` after exactly those ``optimizer.step()`` calls that
+    ran.  The shadows are clones of the trainable parameters taken at construction; the first
+    update copies (``_foreach_copy_``), later ones are ``_foreach_lerp_(shadows, params, 1 - d)``
+    — ``torch.optim.swa_utils.AveragedModel`` with ``get_ema_multi_avg_fn(d)``, bit for bit —
+    with d capped at ``(1 + n) / (10 + n)`` on update n under the warm-up.  Buffers are not
+    averaged."""
+
+    def __init__(self, params, ema_decay, ema_warmup=False, ema_eval=True):
+        self.ema_decay = check_ema_decay(ema_decay)
+        if self.ema_decay is None:
+            raise ValueError("HostEma: ema_decay must be a number with 0 < d < 1, got None")
+        self.ema_warmup = check_ema_flag("ema_warmup", ema_warmup)
+        self.ema_eval = check_ema_flag("ema_eval", ema_eval)
+        self.params = [p for p in params if p.requires_grad]
+        self.shadows = [p.detach().clone() for p in self.params]
+        self.ema_updates = 0
+        self._swapped = False
+
+    @torch.no_grad()
+    def update(self):
+        if self._swapped:
+            raise RuntimeError("HostEma.update: the parameters hold the averaged weights")
+        n = self.ema_updates
+        if n == 0:
+            torch._foreach_copy_(self.shadows, self.params)
+        else:
+            d = self.ema_decay
+            if self.ema_warmup:
+                d = min(d, (1.0 + n) / (10.0 + n))
+            torch._foreach_lerp_(self.shadows, self.params, 1 - d)
+        self.ema_updates = n + 1
+
+    def ema_parameters(self):
+        return list(zip(self.params, self.shadows))
+
+    @torch.no_grad()
+    def swap_ema(self):
+        for p, e in zip(self.params, self.shadows):
+            live = p.detach().clone()
+            p.copy_(e)
+            e.copy_(live)
+        self._swapped = not self._swapped
+
+    @contextlib.contextmanager
+    def averaged(self):
+        self.swap_ema()
+        try:
+            yield self
+        finally:
+            self.swap_ema()
+
+
+def ema_of(optimizer):
+    """What carries an optimizer's weight EMA — the FusedAdam itself with ``ema_decay`` set, or
+    the HostEma hung on a torch optimizer — or None."""
+    if isinstance(optimizer, FusedAdam):
+        return optimizer if optimizer.ema_decay is not None else None
+    return getattr(optimizer, "ema", None)
 
 
 _clip_plans = {}   # (device, span rows) -> _NormPlan of clip_grad_norm_ (a few, oldest dropped)

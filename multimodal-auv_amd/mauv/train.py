@@ -231,6 +231,8 @@ def _scaled_step_host(model, optimizer, gs):
     grad_norm = _host_clip(optimizer) if stepped else None
     gs.step(optimizer)
     gs.update()
+    if stepped:
+        _host_ema_update(optimizer)
     optimizer.zero_grad()
     return stepped, grad_norm
 
@@ -274,6 +276,15 @@ def _host_window(optimizer):
             w = optimizer.__dict__["_mauv_window"] = _HostWindow()
         return w
     return None
+
+
+def _host_ema_update(optimizer):
+    """A host model's torch optimizer carries its weight EMA as ``optimizer.ema``
+    (mauv.optim.HostEma): one update after an ``optimizer.step()`` that ran.  FusedAdam averages
+    inside its own step."""
+    ema = optimizer.__dict__.get("ema")
+    if ema is not None:
+        ema.update()
 
 
 def _average_grads(optimizer, m):
@@ -325,7 +336,14 @@ def mc_train_step(model, inputs_tuple, labels, criterion, optimizer, num_mc, bat
     loss runs no backward and marks the window bad, and the close either zeroes the gradients
     (bad window) or multiplies them by 1 / count once and then clips, unscales and steps as ever.
     BatchNorm statistics, the Philox offset and the KL term (``KL / batch_size * kl_w``) are per
-    micro-batch."""
+    micro-batch.
+
+    With ``FusedAdam(ema_decay=d)`` the gated step also keeps the weight EMA:
+    the same device decision forms the update's weight and the Adam kernel stores each shadow
+    beside its parameter, so the average moves on exactly the steps that happened and this
+    function does nothing for it.  On the host-decided path FusedAdam averages inside its
+    ``step()``; a host model's torch optimizer carries a ``mauv.optim.HostEma`` (``ema``), updated
+    here after exactly those ``optimizer.step()`` calls that ran."""
     inflight = _throttle(model)
     loss, output, predicted, ce, scaled_kl = mc_loss(model, inputs_tuple, labels, criterion,
                                                      num_mc, batch_size, kl_w)
@@ -404,6 +422,7 @@ def mc_train_step(model, inputs_tuple, labels, criterion, optimizer, num_mc, bat
         if stepped:
             grad_norm = _host_clip(optimizer)
             optimizer.step()
+            _host_ema_update(optimizer)
             if grad_norm is None:   # FusedAdam with the option: the norm its own clip measured
                 grad_norm = getattr(optimizer, "last_grad_norm", None)
             optimizer.zero_grad()
@@ -465,6 +484,7 @@ def _host_window_step(model, inputs_tuple, loss, optimizer, win, close_window, l
                 if stepped:
                     grad_norm = _host_clip(optimizer)
                     optimizer.step()
+                    _host_ema_update(optimizer)
                     if grad_norm is None:
                         grad_norm = getattr(optimizer, "last_grad_norm", None)
                     optimizer.zero_grad()
@@ -875,6 +895,7 @@ def train_unimodal_model(model, dataloader, criterion, optimizer, epoch, total_n
                     else:
                         _host_clip(optimizer)
                         optimizer.step()
+                        _host_ema_update(optimizer)
                 lv = loss.item()
                 total_loss += lv
                 correct += int((predicted == labels).sum().item())
