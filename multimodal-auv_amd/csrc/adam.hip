@@ -10,18 +10,13 @@
 //   p -= lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
 // mauv_adam_step_ex is the same launch with torch's other options (amsgrad, maximize, decoupled
 // weight decay) and up to 8 parameter groups, each row naming its group.
-// The gated forms first multiply g by the gate's clip coefficient (global-norm gradient clipping,
-// DESIGN.md §2.36; 1 when it is off).  mauv_adam_step_ex_scaled is the gated launch with dynamic
-// loss scaling (torch.amp.GradScaler's algorithm): the decision also backs the
-// scale off or grows it, and the kernel multiplies g by 1 / scale ahead of the clip coefficient.
-// mauv_accum_note / mauv_adam_step_ex_accum add gradient accumulation: a window
-// of micro-batches is counted in a MauvAccum beside the gate, the closing call takes the same
-// decision once per window and the kernel multiplies g by 1 / micro between the two factors.
-// mauv_adam_step_ex_ema adds an exponential moving average of the weights: the
-// same decision also forms the average's weight in a MauvEma beside the gate when, and only when,
-// it is "Adam step", and the kernel moves each row's shadow tensor towards the new p it holds in a
-// register.  mauv_ema_update / mauv_ema_swap are the same element update at a host-given weight
-// and the in-place exchange of parameters and shadows.
+// The gated forms run ONE single-thread decision kernel first, then the Adam launch, which
+// multiplies g as it loads it by 1 / scale (dynamic loss scaling, §2.37), 1 / micro (gradient
+// accumulation, §2.39; mauv_accum_note counts the window's other micro-batches) and the clip
+// coefficient (global-norm clipping, §2.36), each 1 when off, and moves each row's shadow towards
+// the new p (weight EMA, §2.42).  The four gated all-groups entries differ only in which of the
+// optional state pointers they take.  mauv_ema_update / mauv_ema_swap are the
+// EMA's element update at a host-given weight and the in-place exchange of parameters and shadows.
 #include "mauv_common.h"
 
 using namespace mauv;
@@ -125,43 +120,8 @@ __device__ __forceinline__ void gate_take_step(MauvStepGate* g, float lr, float 
 //                       (mode 2 zeroes it when it was clean before; a poisoned arena stays)
 //   grads non-finite -> no step, no zero_grad: the arena keeps them ("poisoned")
 //   otherwise        -> Adam at step count t+1, then zero_grad (mode 3)
-// and the non-finite counter is reset for the next scan.  Every decision also writes the clip
-// coefficient the Adam kernels multiply the gradient by: torch's clip_grad_norm_ formula over
-// the scan's grad_norm when max_norm > 0, else 1 (unused when the step is skipped).
-// `ok_loss`: the loss was finite (a window of micro-batches: every one of them); `loss_skips`:
-// what a bad loss adds to skipped_loss (1, or 0 when mauv_accum_note counted it already); `avg`:
-// 1, or 1 / micro of a closing window, which scales the scanned norm of the summed gradients.
-__device__ __forceinline__ void gate_decide(MauvStepGate* g, int ok_loss, int loss_skips,
-                                            float avg, float lr, float beta1, float beta2) {
-  const int ok_grad = g->nonfinite == 0;
-  if (ok_loss && ok_grad) {
-    gate_take_step(g, lr, beta1, beta2);
-  } else {
-    g->stepped = 0;
-    if (!ok_loss) {
-      g->mode = g->poisoned ? 0 : 2;
-      g->skipped_loss += loss_skips;
-    } else {
-      g->mode = 0;
-      g->poisoned = 1;
-      g->skipped_grad += 1;
-    }
-  }
-  g->nonfinite = 0;
-  if (g->max_norm > 0.f) {
-    if (avg != 1.0f) g->grad_norm = __fmul_rn(g->grad_norm, avg);
-    g->clip_coef = clip_coef(g->max_norm, g->grad_norm);
-  } else {
-    g->clip_coef = 1.0f;
-  }
-}
-
-__global__ void step_gate_kernel(MauvStepGate* g, float lr, float beta1, float beta2) {
-  gate_decide(g, g->ok_loss != 0, 1, 1.0f, lr, beta1, beta2);
-}
-
-// The same decision with a loss scaler beside the gate (one thread).  The
-// arena holds the gradients of loss * scale:
+// With a loss scaler `s` beside the gate the arena holds the gradients of
+// loss * scale, and:
 //   loss non-finite  -> as above; the scaler is not touched (a NaN input is no overflow)
 //   grads non-finite -> an overflow of the scaled gradients: no step, the arena is zeroed
 //                       (mode 2; never "poisoned": the next batch starts clean, as GradScaler
@@ -170,57 +130,75 @@ __global__ void step_gate_kernel(MauvStepGate* g, float lr, float beta1, float b
 //                       growth_interval: scale *= growth_factor if that is finite (torch's
 //                       _amp_update_scale_), growth_tracker = 0
 // growth_interval == 0 is a static scale: only the counters move.  unscale = 1 / scale is formed
-// from the scale the backward ran with, before it changes; the scanned norm is the scaled
-// gradients', so grad_norm is rewritten as the true norm before the clip coefficient is formed.
-__device__ __forceinline__ void gate_decide_scaled(MauvStepGate* g, MauvLossScale* s, int ok_loss,
-                                                   int loss_skips, float avg, float lr,
-                                                   float beta1, float beta2) {
+// from the scale the backward ran with, before it changes.
+// Then the non-finite counter is reset for the next scan, and every decision writes the clip
+// coefficient the Adam kernels multiply the gradient by: torch's clip_grad_norm_ formula over
+// the scan's grad_norm when max_norm > 0, else 1 (unused when the step is skipped).  The scanned
+// norm is that of the scaled, summed gradients, so grad_norm is first rewritten as the true norm.
+// `ok_loss`: the loss was finite (a window of micro-batches: every one of them); `loss_skips`:
+// what a bad loss adds to skipped_loss (1, or 0 when mauv_accum_note counted it already); `avg`:
+// 1, or 1 / micro of a closing window.
+__device__ __forceinline__ void gate_decide(MauvStepGate* g, MauvLossScale* s, int ok_loss,
+                                            int loss_skips, float avg, float lr, float beta1,
+                                            float beta2) {
   const int ok_grad = g->nonfinite == 0;
-  const float scale = s->scale;
-  const float unscale = (float)(1.0 / (double)scale);
-  const bool dynamic = s->growth_interval != 0;
-  s->unscale = unscale;
-  if (!ok_loss) {
-    g->stepped = 0;
-    g->mode = g->poisoned ? 0 : 2;
-    g->skipped_loss += loss_skips;
-  } else if (!ok_grad) {
-    g->stepped = 0;
-    g->mode = 2;
-    g->poisoned = 0;
-    g->skipped_grad += 1;
-    s->overflows += 1;
-    if (dynamic) {
-      s->scale = (float)((double)scale * (double)s->backoff_factor);   // torch's rounding
-      s->growth_tracker = 0;
+  float unscale = 1.0f;
+  if (!s) {
+    if (ok_loss && ok_grad) {
+      gate_take_step(g, lr, beta1, beta2);
+    } else {
+      g->stepped = 0;
+      if (!ok_loss) {
+        g->mode = g->poisoned ? 0 : 2;
+        g->skipped_loss += loss_skips;
+      } else {
+        g->mode = 0;
+        g->poisoned = 1;
+        g->skipped_grad += 1;
+      }
     }
   } else {
-    gate_take_step(g, lr, beta1, beta2);
-    if (dynamic) {
-      const int ok_steps = s->growth_tracker + 1;
-      if (ok_steps == s->growth_interval) {
-        const float grown = (float)((double)scale * (double)s->growth_factor);
-        if (isfinite(grown)) s->scale = grown;
+    const float scale = s->scale;
+    const bool dynamic = s->growth_interval != 0;
+    unscale = (float)(1.0 / (double)scale);
+    s->unscale = unscale;
+    if (!ok_loss) {
+      g->stepped = 0;
+      g->mode = g->poisoned ? 0 : 2;
+      g->skipped_loss += loss_skips;
+    } else if (!ok_grad) {
+      g->stepped = 0;
+      g->mode = 2;
+      g->poisoned = 0;
+      g->skipped_grad += 1;
+      s->overflows += 1;
+      if (dynamic) {
+        s->scale = (float)((double)scale * (double)s->backoff_factor);   // torch's rounding
         s->growth_tracker = 0;
-        s->growths += 1;
-      } else {
-        s->growth_tracker = ok_steps;
+      }
+    } else {
+      gate_take_step(g, lr, beta1, beta2);
+      if (dynamic) {
+        const int ok_steps = s->growth_tracker + 1;
+        if (ok_steps == s->growth_interval) {
+          const float grown = (float)((double)scale * (double)s->growth_factor);
+          if (isfinite(grown)) s->scale = grown;
+          s->growth_tracker = 0;
+          s->growths += 1;
+        } else {
+          s->growth_tracker = ok_steps;
+        }
       }
     }
   }
   g->nonfinite = 0;
   if (g->max_norm > 0.f) {
-    g->grad_norm = __fmul_rn(g->grad_norm, unscale);   // (a NaN stays NaN)
+    if (s) g->grad_norm = __fmul_rn(g->grad_norm, unscale);   // (a NaN stays NaN)
     if (avg != 1.0f) g->grad_norm = __fmul_rn(g->grad_norm, avg);
     g->clip_coef = clip_coef(g->max_norm, g->grad_norm);
   } else {
     g->clip_coef = 1.0f;
   }
-}
-
-__global__ void step_gate_scaled_kernel(MauvStepGate* g, MauvLossScale* s, float lr, float beta1,
-                                        float beta2) {
-  gate_decide_scaled(g, s, g->ok_loss != 0, 1, 1.0f, lr, beta1, beta2);
 }
 
 // ---- gradient accumulation -------------------------------------------------
@@ -236,49 +214,41 @@ __global__ void accum_note_kernel(MauvStepGate* g, MauvAccum* a) {
   g->mode = 0;
 }
 
-// The closing micro-batch (one thread): folded in as above, then the decision of the kernels
-// above once for the window, "loss ok" being "no micro-batch of it had a non-finite loss".
-__device__ __forceinline__ void accum_close(MauvStepGate* g, MauvLossScale* s, MauvAccum* a,
-                                            float lr, float beta1, float beta2) {
-  const int bad_now = g->ok_loss == 0;
-  const int micro = a->micro + 1, bad = a->bad_loss + bad_now;
-  const float avg = (float)(1.0 / (double)micro);
-  a->avg = avg;
-  if (s) gate_decide_scaled(g, s, bad == 0, bad_now, avg, lr, beta1, beta2);
-  else gate_decide(g, bad == 0, bad_now, avg, lr, beta1, beta2);
-  a->windows += 1;
-  a->dropped += bad != 0;
-  a->micro = 0;
-  a->bad_loss = 0;
-}
-
-__global__ void step_gate_accum_kernel(MauvStepGate* g, MauvLossScale* s, MauvAccum* a, float lr,
-                                       float beta1, float beta2) {
-  accum_close(g, s, a, lr, beta1, beta2);
-}
-
-// ---- weight EMA ------------------------------------------------------------
-// The decision of the kernels above (window, scaler or neither), then, on the same thread and
-// only when it is "Adam step" (mode bit 1), the weight of this update: 1 for the first one
-// (torch's AveragedModel copies), else 1 - decay, the decay capped at (1 + n) / (10 + n) under
-// timm's warm-up.  Every other decision leaves the MauvEma as it is.
-__global__ void step_gate_ema_kernel(MauvStepGate* g, MauvLossScale* s, MauvAccum* a, MauvEma* e,
-                                     float lr, float beta1, float beta2) {
-  if (a) accum_close(g, s, a, lr, beta1, beta2);
-  else if (s) gate_decide_scaled(g, s, g->ok_loss != 0, 1, 1.0f, lr, beta1, beta2);
-  else gate_decide(g, g->ok_loss != 0, 1, 1.0f, lr, beta1, beta2);
-  if (!(g->mode & 1)) return;
-  const int n = e->updates;
-  float w = 1.0f;
-  if (n != 0) {
-    double d = (double)e->decay;
-    if (e->warmup) d = fmin(d, (1.0 + (double)n) / (10.0 + (double)n));
-    w = (float)(1.0 - d);
+// The decision kernel of every gated entry (one thread); `s`, `a` and `e` may each be NULL.
+// With a window `a` this is its closing micro-batch: folded in as above, then one decision for
+// the window, "loss ok" being "no micro-batch of it had a non-finite loss".  With a weight EMA `e`
+// (DESIGN.md §2.42), and only when the decision is "Adam step" (mode bit 1), the weight of this
+// update: 1 for the first one (torch's AveragedModel copies), else 1 - decay, the decay capped at
+// (1 + n) / (10 + n) under timm's warm-up.  Every other decision leaves the MauvEma as it is.
+__global__ void step_gate_kernel(MauvStepGate* g, MauvLossScale* s, MauvAccum* a, MauvEma* e,
+                                 float lr, float beta1, float beta2) {
+  if (a) {
+    const int bad_now = g->ok_loss == 0;
+    const int micro = a->micro + 1, bad = a->bad_loss + bad_now;
+    const float avg = (float)(1.0 / (double)micro);
+    a->avg = avg;
+    gate_decide(g, s, bad == 0, bad_now, avg, lr, beta1, beta2);
+    a->windows += 1;
+    a->dropped += bad != 0;
+    a->micro = 0;
+    a->bad_loss = 0;
+  } else {
+    gate_decide(g, s, g->ok_loss != 0, 1, 1.0f, lr, beta1, beta2);
   }
-  e->weight = w;
-  e->updates = n + 1;
+  if (e && (g->mode & 1)) {
+    const int n = e->updates;
+    float w = 1.0f;
+    if (n != 0) {
+      double d = (double)e->decay;
+      if (e->warmup) d = fmin(d, (1.0 + (double)n) / (10.0 + (double)n));
+      w = (float)(1.0 - d);
+    }
+    e->weight = w;
+    e->updates = n + 1;
+  }
 }
 
+// ---- weight EMA: the element code ------------------------------------------------------------
 // The new p as the average reads it: the value the Adam update has settled on, opaque to the
 // compiler, so that the update's own arithmetic (which products it fuses) is compiled exactly as
 // in the instantiations without an average and p keeps their bits.
@@ -545,10 +515,62 @@ MAUV_API int mauv_adam_step_gated(const MauvAdamEntry* table, int n, float lr, f
                                   float beta2, float eps, float weight_decay, MauvStepGate* gate,
                                   hipStream_t stream) {
   if (n <= 0 || n > 65535 || !gate) { set_error("adam_step_gated: bad table size / gate"); return kErrArg; }
-  hipLaunchKernelGGL(step_gate_kernel, dim3(1), dim3(1), 0, stream, gate, lr, beta1, beta2);
+  hipLaunchKernelGGL(step_gate_kernel, dim3(1), dim3(1), 0, stream, gate, nullptr, nullptr,
+                     nullptr, lr, beta1, beta2);
   hipLaunchKernelGGL(adam_kernel<true>, dim3(64, n), dim3(256), 0, stream, table, lr, beta1,
                      beta2, eps, weight_decay, 0.f, 1.f, (const MauvStepGate*)gate);
   return check_launch("adam_step_gated");
+}
+
+// The table and group checks of every all-groups entry, `name` being the entry's own.
+static bool ex_args_ok(const char* name, const MauvAdamEntryEx* table, int n,
+                       const MauvAdamGroup* groups, int n_groups) {
+  if (n <= 0 || n > 65535 || !table) {
+    set_error(std::string(name) + ": bad table size");
+    return false;
+  }
+  if (n_groups < 1 || n_groups > MAUV_ADAM_MAX_GROUPS || !groups) {
+    set_error(std::string(name) + ": 1..8 parameter groups");
+    return false;
+  }
+  return true;
+}
+
+// The groups by value; step == 0: gated, the constants come from the gate.
+static void fill_groups(AdamGroupsArg& ga, const MauvAdamGroup* groups, int n_groups,
+                        long long step) {
+  for (int i = 0; i < n_groups; ++i) {
+    ga.g[i] = groups[i];
+    ga.step_size[i] = 0.f;
+    ga.bc2_sqrt[i] = 1.f;
+    if (step) {
+      const double bc1 = 1.0 - pow((double)groups[i].beta1, (double)step);
+      const double bc2 = 1.0 - pow((double)groups[i].beta2, (double)step);
+      ga.step_size[i] = (float)(groups[i].lr / bc1);
+      ga.bc2_sqrt[i] = (float)sqrt(bc2);
+    }
+  }
+}
+
+// Every gated all-groups entry: the decision (scaler, acc and ema may each be NULL), then the
+// Adam launch reading 1 / scale, 1 / micro and the clip coefficient, and moving the rows' shadows
+// when both ema and ema_rows are given.
+static int launch_gated_ex(const char* name, const MauvAdamEntryEx* table, int n,
+                           const MauvAdamGroup* groups, int n_groups, MauvStepGate* gate,
+                           MauvLossScale* scaler, MauvAccum* acc, float* const* ema_rows,
+                           MauvEma* ema, hipStream_t stream) {
+  if (!ex_args_ok(name, table, n, groups, n_groups)) return kErrArg;
+  if (!gate) { set_error(std::string(name) + ": no gate"); return kErrArg; }
+  if (!ema || !ema_rows) ema = nullptr, ema_rows = nullptr;
+  AdamGroupsArg ga = {};
+  fill_groups(ga, groups, n_groups, 0);
+  hipLaunchKernelGGL(step_gate_kernel, dim3(1), dim3(1), 0, stream, gate, scaler, acc, ema,
+                     groups[0].lr, groups[0].beta1, groups[0].beta2);
+  auto kernel = ema ? adam_ex_kernel<true, true> : adam_ex_kernel<true, false>;
+  hipLaunchKernelGGL(kernel, dim3(64, n), dim3(256), 0, stream, table, ga, n_groups,
+                     (const MauvStepGate*)gate, (const MauvLossScale*)scaler,
+                     (const MauvAccum*)acc, ema_rows, (const MauvEma*)ema);
+  return check_launch(name);
 }
 
 // Every Adam option and up to MAUV_ADAM_MAX_GROUPS parameter groups in one launch (mauv.h).
@@ -557,65 +579,26 @@ MAUV_API int mauv_adam_step_gated(const MauvAdamEntry* table, int n, float lr, f
 MAUV_API int mauv_adam_step_ex(const MauvAdamEntryEx* table, int n, const MauvAdamGroup* groups,
                                int n_groups, long long step, MauvStepGate* gate,
                                hipStream_t stream) {
-  if (n <= 0 || n > 65535 || !table) { set_error("adam_step_ex: bad table size"); return kErrArg; }
-  if (n_groups < 1 || n_groups > MAUV_ADAM_MAX_GROUPS || !groups) {
-    set_error("adam_step_ex: 1..8 parameter groups");
-    return kErrArg;
-  }
-  if (!gate && step < 1) { set_error("adam_step_ex: ungated step < 1"); return kErrArg; }
+  if (gate)
+    return launch_gated_ex("adam_step_ex", table, n, groups, n_groups, gate, nullptr, nullptr,
+                           nullptr, nullptr, stream);
+  if (!ex_args_ok("adam_step_ex", table, n, groups, n_groups)) return kErrArg;
+  if (step < 1) { set_error("adam_step_ex: ungated step < 1"); return kErrArg; }
   AdamGroupsArg ga = {};
-  for (int i = 0; i < n_groups; ++i) {
-    ga.g[i] = groups[i];
-    ga.step_size[i] = 0.f;
-    ga.bc2_sqrt[i] = 1.f;
-    if (!gate) {
-      const double bc1 = 1.0 - pow((double)groups[i].beta1, (double)step);
-      const double bc2 = 1.0 - pow((double)groups[i].beta2, (double)step);
-      ga.step_size[i] = (float)(groups[i].lr / bc1);
-      ga.bc2_sqrt[i] = (float)sqrt(bc2);
-    }
-  }
-  if (gate) {
-    hipLaunchKernelGGL(step_gate_kernel, dim3(1), dim3(1), 0, stream, gate, groups[0].lr,
-                       groups[0].beta1, groups[0].beta2);
-    hipLaunchKernelGGL((adam_ex_kernel<true, false>), dim3(64, n), dim3(256), 0, stream, table, ga,
-                       n_groups, (const MauvStepGate*)gate, nullptr, nullptr, nullptr, nullptr);
-  } else {
-    hipLaunchKernelGGL((adam_ex_kernel<false, false>), dim3(64, n), dim3(256), 0, stream, table, ga,
-                       n_groups, nullptr, nullptr, nullptr, nullptr, nullptr);
-  }
+  fill_groups(ga, groups, n_groups, step);
+  hipLaunchKernelGGL((adam_ex_kernel<false, false>), dim3(64, n), dim3(256), 0, stream, table, ga,
+                     n_groups, nullptr, nullptr, nullptr, nullptr, nullptr);
   return check_launch("adam_step_ex");
 }
 
-// The gated mauv_adam_step_ex with a loss scaler (mauv.h): the scaled decision, then the same
-// Adam launch reading 1 / scale beside the clip coefficient.  scaler == NULL is exactly
+// The gated mauv_adam_step_ex with a loss scaler (mauv.h).  scaler == NULL is exactly
 // mauv_adam_step_ex(table, n, groups, n_groups, 0, gate, stream).
 MAUV_API int mauv_adam_step_ex_scaled(const MauvAdamEntryEx* table, int n,
                                       const MauvAdamGroup* groups, int n_groups,
                                       MauvStepGate* gate, MauvLossScale* scaler,
                                       hipStream_t stream) {
-  if (n <= 0 || n > 65535 || !table) {
-    set_error("adam_step_ex_scaled: bad table size");
-    return kErrArg;
-  }
-  if (n_groups < 1 || n_groups > MAUV_ADAM_MAX_GROUPS || !groups) {
-    set_error("adam_step_ex_scaled: 1..8 parameter groups");
-    return kErrArg;
-  }
-  if (!gate) { set_error("adam_step_ex_scaled: no gate"); return kErrArg; }
-  if (!scaler) return mauv_adam_step_ex(table, n, groups, n_groups, 0, gate, stream);
-  AdamGroupsArg ga = {};
-  for (int i = 0; i < n_groups; ++i) {
-    ga.g[i] = groups[i];
-    ga.step_size[i] = 0.f;
-    ga.bc2_sqrt[i] = 1.f;
-  }
-  hipLaunchKernelGGL(step_gate_scaled_kernel, dim3(1), dim3(1), 0, stream, gate, scaler,
-                     groups[0].lr, groups[0].beta1, groups[0].beta2);
-  hipLaunchKernelGGL((adam_ex_kernel<true, false>), dim3(64, n), dim3(256), 0, stream, table, ga,
-                     n_groups, (const MauvStepGate*)gate, (const MauvLossScale*)scaler, nullptr,
-                     nullptr, nullptr);
-  return check_launch("adam_step_ex_scaled");
+  return launch_gated_ex("adam_step_ex_scaled", table, n, groups, n_groups, gate, scaler, nullptr,
+                         nullptr, nullptr, stream);
 }
 
 // A micro-batch inside an accumulation window (mauv.h): one single-thread launch, no scan and
@@ -626,68 +609,25 @@ MAUV_API int mauv_accum_note(MauvStepGate* gate, MauvAccum* acc, hipStream_t str
   return check_launch("accum_note");
 }
 
-// The closing micro-batch of an accumulation window (mauv.h): the window's decision, then the
-// Adam launch reading 1 / micro between 1 / scale and the clip coefficient.  acc == NULL is
-// exactly mauv_adam_step_ex_scaled(table, n, groups, n_groups, gate, scaler, stream).
+// The closing micro-batch of an accumulation window (mauv.h).  acc == NULL is exactly
+// mauv_adam_step_ex_scaled(table, n, groups, n_groups, gate, scaler, stream).
 MAUV_API int mauv_adam_step_ex_accum(const MauvAdamEntryEx* table, int n,
                                      const MauvAdamGroup* groups, int n_groups,
                                      MauvStepGate* gate, MauvLossScale* scaler, MauvAccum* acc,
                                      hipStream_t stream) {
-  if (n <= 0 || n > 65535 || !table) {
-    set_error("adam_step_ex_accum: bad table size");
-    return kErrArg;
-  }
-  if (n_groups < 1 || n_groups > MAUV_ADAM_MAX_GROUPS || !groups) {
-    set_error("adam_step_ex_accum: 1..8 parameter groups");
-    return kErrArg;
-  }
-  if (!gate) { set_error("adam_step_ex_accum: no gate"); return kErrArg; }
-  if (!acc) return mauv_adam_step_ex_scaled(table, n, groups, n_groups, gate, scaler, stream);
-  AdamGroupsArg ga = {};
-  for (int i = 0; i < n_groups; ++i) {
-    ga.g[i] = groups[i];
-    ga.step_size[i] = 0.f;
-    ga.bc2_sqrt[i] = 1.f;
-  }
-  hipLaunchKernelGGL(step_gate_accum_kernel, dim3(1), dim3(1), 0, stream, gate, scaler, acc,
-                     groups[0].lr, groups[0].beta1, groups[0].beta2);
-  hipLaunchKernelGGL((adam_ex_kernel<true, false>), dim3(64, n), dim3(256), 0, stream, table, ga,
-                     n_groups, (const MauvStepGate*)gate, (const MauvLossScale*)scaler,
-                     (const MauvAccum*)acc, nullptr, nullptr);
-  return check_launch("adam_step_ex_accum");
+  return launch_gated_ex("adam_step_ex_accum", table, n, groups, n_groups, gate, scaler, acc,
+                         nullptr, nullptr, stream);
 }
 
-// The gated step with a weight EMA (mauv.h): the decision of mauv_adam_step_ex_accum (scaler and
-// acc may each be NULL) also forms the average's weight, then the Adam launch moves every row's
-// shadow.  ema == NULL or ema_rows == NULL is exactly mauv_adam_step_ex_accum(table, n, groups,
-// n_groups, gate, scaler, acc, stream).
+// The gated step with a weight EMA (mauv.h); scaler and acc may each be NULL.  ema == NULL or
+// ema_rows == NULL is exactly mauv_adam_step_ex_accum(table, n, groups, n_groups, gate, scaler,
+// acc, stream).
 MAUV_API int mauv_adam_step_ex_ema(const MauvAdamEntryEx* table, int n,
                                    const MauvAdamGroup* groups, int n_groups, MauvStepGate* gate,
                                    MauvLossScale* scaler, MauvAccum* acc, float* const* ema_rows,
                                    MauvEma* ema, hipStream_t stream) {
-  if (n <= 0 || n > 65535 || !table) {
-    set_error("adam_step_ex_ema: bad table size");
-    return kErrArg;
-  }
-  if (n_groups < 1 || n_groups > MAUV_ADAM_MAX_GROUPS || !groups) {
-    set_error("adam_step_ex_ema: 1..8 parameter groups");
-    return kErrArg;
-  }
-  if (!gate) { set_error("adam_step_ex_ema: no gate"); return kErrArg; }
-  if (!ema || !ema_rows)
-    return mauv_adam_step_ex_accum(table, n, groups, n_groups, gate, scaler, acc, stream);
-  AdamGroupsArg ga = {};
-  for (int i = 0; i < n_groups; ++i) {
-    ga.g[i] = groups[i];
-    ga.step_size[i] = 0.f;
-    ga.bc2_sqrt[i] = 1.f;
-  }
-  hipLaunchKernelGGL(step_gate_ema_kernel, dim3(1), dim3(1), 0, stream, gate, scaler, acc, ema,
-                     groups[0].lr, groups[0].beta1, groups[0].beta2);
-  hipLaunchKernelGGL((adam_ex_kernel<true, true>), dim3(64, n), dim3(256), 0, stream, table, ga,
-                     n_groups, (const MauvStepGate*)gate, (const MauvLossScale*)scaler,
-                     (const MauvAccum*)acc, ema_rows, (const MauvEma*)ema);
-  return check_launch("adam_step_ex_ema");
+  return launch_gated_ex("adam_step_ex_ema", table, n, groups, n_groups, gate, scaler, acc,
+                         ema_rows, ema, stream);
 }
 
 // The average's element update at a host-given weight over a device table of (shadow, parameter,

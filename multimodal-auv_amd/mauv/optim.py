@@ -15,8 +15,9 @@ One parameter group with the three options off steps through ``mauv_adam_step`` 
 table of (param, grad, exp_avg, exp_avg_sq, numel) rows.  Anything else — options, several
 groups — steps through ``mauv_adam_step_ex``: all groups in ONE launch (eight groups per launch),
 rows of (param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq, numel, group) and the groups' lr /
-betas / eps / weight_decay / flags by value.  Tables are rebuilt only when a pointer changes.
-Parameters whose ``.grad`` is None are skipped, like torch.
+betas / eps / weight_decay / flags by value.  Either way the step's tensors, device table and step
+count are cached in a ``_Plan``, rebuilt only when a pointer changes.  Parameters whose ``.grad``
+is None are skipped, like torch.
 
 ``step_gated(gate)`` is the training loop's form (mauv.train.mc_train_step): the decision of
 multimodal.py:133-145 — skip on a non-finite loss, skip the step and the zero_grad on
@@ -39,9 +40,9 @@ adds dynamic loss scaling, ``torch.amp.GradScaler``'s algorithm, for f16 trainin
 §2.37).  It is a plain attribute like ``max_grad_norm``: no ``param_groups`` key, not in
 ``state_dict()`` (the scaler has its own).  The caller runs the backward on
 ``opt.loss_scale.scale(loss)`` (mauv.train does).  The gated form then hands the scaler's device
-state to ``mauv_adam_step_ex_scaled``: the decision skips the step and zeroes the gradients on an
-overflow, backs the scale off or grows it, and the kernel multiplies each gradient by 1 / scale
-ahead of the clip coefficient; ``last_grad_norm`` is the norm of the unscaled gradients.
+state to the kernel: the decision skips the step and zeroes the gradients on an overflow, backs
+the scale off or grows it, and the kernel multiplies each gradient by 1 / scale ahead of the
+clip coefficient; ``last_grad_norm`` is the norm of the unscaled gradients.
 ``step()`` with a scaler set goes through the same device decision on a gate of its own over the
 live parameters (``ok_loss`` = 1): it scans, unscales, clips, steps AND zeroes the gradients
 (stepped or skipped, as GradScaler's ``step`` followed by ``zero_grad``), a skipped step does not
@@ -53,13 +54,12 @@ step on scaled gradients.
 (DESIGN.md §2.39): a plain attribute like ``max_grad_norm``, reassignable between windows, no
 ``param_groups`` key and not in ``state_dict()``.  With K > 1 ``step_gated(gate)`` closes a window
 every K-th call (or when told to, ``close=True``); the other calls queue ``mauv_accum_note`` only:
-no scan, no Adam launch.  The closing call takes the all-groups entry ``mauv_adam_step_ex_accum``:
-one decision for the window (a window holding any non-finite loss is dropped whole), the loss
-scaler moves once per window, and the kernel multiplies each gradient by 1 / micro-batches between
-1 / scale and the clip coefficient, so the step is Adam on the mean of the micro-batch gradients.
-``zero_grad()`` also abandons the open window.  The ungated ``step()`` and
-``mauv.amp.LossScaler.step(opt)`` in a user's own loop do not look at the option: such a loop
-divides its gradients itself.
+no scan, no Adam launch.  The closing call is the step: one decision for the window (a window
+holding any non-finite loss is dropped whole), the loss scaler moves once per window, and the
+kernel multiplies each gradient by 1 / micro-batches between 1 / scale and the clip coefficient,
+so the step is Adam on the mean of the micro-batch gradients.  ``zero_grad()`` also abandons the
+open window.  The ungated ``step()`` and ``mauv.amp.LossScaler.step(opt)`` in a user's own loop
+do not look at the option: such a loop divides its gradients itself.
 
 ``ema_decay`` (None, or a number with 0 < d < 1) keeps an exponential moving average (EMA) of the
 weights beside Adam, what ``torch.optim.swa_utils.AveragedModel`` with
@@ -71,10 +71,10 @@ three are plain attributes like ``max_grad_norm``, no ``param_groups`` keys.  Th
 parameter is ``state[p]["ema"]``, created beside ``exp_avg`` as a clone of the parameter (frozen
 parameters get none; with the option off the key never appears), so ``state_dict()`` carries the
 shadows, and beside them a top-level ``"ema_updates"``; it still loads into torch.optim.Adam and
-back.  The gated form takes the all-groups entry ``mauv_adam_step_ex_ema``: the device decision
-also forms the weight, in a ``MauvEma`` beside the gate, and the Adam kernel stores the shadow
-beside the new parameter it holds in a register — no extra pass and no host wait; a skipped step
-(bad loss, non-finite gradients, overflow, dropped window) moves nothing.  The ungated ``step()``
+back.  In the gated form the device decision also forms the weight, in a ``MauvEma`` beside the
+gate, and the Adam kernel stores the shadow beside the new parameter it holds in a register — no
+extra pass and no host wait; a skipped step (bad loss, non-finite gradients, overflow, dropped
+window) moves nothing.  The ungated ``step()``
 is decided on the host: its Adam launches are followed by ``mauv_ema_update`` over the same live
 parameters at the weight of a host count kept equal to the device rule — ONE EXTRA PASS over
 parameters and shadows.  ``step()`` with a loss scaler takes the gated entry, EMA included.
@@ -86,6 +86,7 @@ not averaged — AveragedModel's default: under the swap the live buffers serve.
 """
 import contextlib
 import ctypes
+import functools
 import math
 import numbers
 
@@ -157,7 +158,7 @@ def check_ema_flag(name, v):
 
 def ema_weight(n, decay, warmup):
     """The weight of EMA update number ``n`` (0-based) as the device forms it (adam.hip
-    step_gate_ema_kernel): 1 for the first update, else (float)(1 - d) with d the fp32 decay,
+    step_gate_kernel): 1 for the first update, else (float)(1 - d) with d the fp32 decay,
     capped at (1 + n) / (10 + n) under the warm-up."""
     if n == 0:
         return 1.0
@@ -206,6 +207,75 @@ def _kind(norm_type):
     return 1 if norm_type == math.inf else 0
 
 
+def word(struct, i, fp32=False):
+    """Word ``i`` of a device struct kept as an int32 tensor (a gate, MauvAccum, MauvEma): a
+    one-element view, as int32 or as the fp32 it holds."""
+    w = struct[i:i + 1]
+    return w.view(torch.float32) if fp32 else w
+
+
+class _Checked:
+    """A plain attribute validated on assignment.  The value lives in the instance ``__dict__``
+    and reads as ``default`` before ``__init__`` has set it: ``Optimizer.__init__`` calls
+    ``add_param_group``, and unpickling bypasses ``__init__``."""
+
+    def __init__(self, check_fn, default=None):
+        self.check_fn, self.default = check_fn, default
+
+    def __set_name__(self, owner, name):
+        self.key = "_" + name
+
+    def __get__(self, obj, owner=None):
+        return self if obj is None else obj.__dict__.get(self.key, self.default)
+
+    def __set__(self, obj, v):
+        obj.__dict__[self.key] = self.check_fn(v)
+
+
+class _Plan:
+    """What one Adam launch set was built over, cached so that the next step over the same
+    tensors skips the per-parameter Python work (checks, one .item() per step counter, table
+    rows).  It holds strong references to the moment (and shadow) tensors the device table points
+    at, and serves only while the state still holds exactly those tensors: a cleared / replaced
+    state drops to the slow path instead of writing through stale pointers.  ``layout`` is None
+    for the 5-column rows of one plain group (mauv_adam_step / _gated); otherwise the rows have 7
+    columns, ``chunks`` lists the launches as (first row, rows, group indices) — at most
+    MAX_GROUPS groups each, a row's group column counting within its launch — and, with the
+    weight EMA on, ``shadows`` / ``shadow_table`` are the rows' shadow tensors and the device
+    table of their pointers.  ``steps`` is the CPU tensor every ``state[p]["step"]`` is a 0-dim
+    view of (still float tensors, torch.optim.Adam-compatible), at count ``t``."""
+    __slots__ = ("ptrs", "gptrs", "moments", "shadows", "state_id", "t", "table", "steps",
+                 "layout", "chunks", "shadow_table", "ident")
+
+    def valid_for(self, opt, live, layout):
+        if self.state_id != id(opt.state) or len(self.ptrs) != len(live) or self.layout != layout:
+            return False
+        if [p.data_ptr() for p in live] != self.ptrs or \
+                [p.grad.data_ptr() for p in live] != self.gptrs:
+            return False
+        if layout is not None and (self.shadows is None) != (opt.ema_decay is None):
+            return False
+        try:
+            for p, mom in zip(live, self.moments):
+                st = opt.state[p]
+                if st["exp_avg"] is not mom[0] or st["exp_avg_sq"] is not mom[1]:
+                    return False
+                if len(mom) == 3 and st["max_exp_avg_sq"] is not mom[2]:
+                    return False
+            for p, sh in zip(live, self.shadows or ()):
+                if opt.state[p]["ema"] is not sh:
+                    return False
+        except KeyError:
+            return False
+        return True
+
+    def advance(self):
+        """The next step count, in the plan and in every parameter's state["step"]."""
+        self.t += 1
+        self.steps.add_(1.0)
+        return self.t
+
+
 class FusedAdam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
                  amsgrad=False, *, foreach=None, maximize=False, capturable=False,
@@ -245,75 +315,23 @@ class FusedAdam(torch.optim.Optimizer):
                                       amsgrad=amsgrad, maximize=maximize, foreach=foreach,
                                       capturable=capturable, differentiable=differentiable,
                                       fused=fused, decoupled_weight_decay=decoupled_weight_decay))
-        self._tables = {}
-        # per group: the tensors of the last step when every live parameter shared one step
-        # count — the next step with the same tensors skips the per-parameter Python work
-        # (checks, one .item() per step counter, table key).  The entry holds strong references
-        # to the moment tensors the device table points at, and is used only while the state
-        # still holds exactly those tensors (a cleared / replaced state drops to the slow path
-        # instead of writing through stale pointers).
+        # key 0 (one plain group) or EX (all groups) -> the _Plan of the last step, when every
+        # live parameter shared one step count; else _split[key] holds one plan per distinct
+        # count, by position, and every step takes the slow path
         self._fast = {}
+        self._split = {}
         self._gate = None          # device MauvStepGate (int32[16]) of the gated form
         self._gate_dirty = False   # the gate's step count is ahead of state["step"]
         self._gate_params = None
         self._gate_live = None     # [(parameter, group index)] the gate was built over
 
-    @property
-    def max_grad_norm(self):
-        return self.__dict__.get("_max_grad_norm")
-
-    @max_grad_norm.setter
-    def max_grad_norm(self, v):
-        self.__dict__["_max_grad_norm"] = check_max_grad_norm(v)
-
-    @property
-    def grad_norm_type(self):
-        return self.__dict__.get("_grad_norm_type", 2.0)
-
-    @grad_norm_type.setter
-    def grad_norm_type(self, v):
-        self.__dict__["_grad_norm_type"] = check_grad_norm_type(v)
-
-    @property
-    def loss_scale(self):
-        """The optimizer's ``mauv.amp.LossScaler``, or None."""
-        return self.__dict__.get("_loss_scale")
-
-    @loss_scale.setter
-    def loss_scale(self, v):
-        self.__dict__["_loss_scale"] = as_loss_scaler(v)
-
-    @property
-    def grad_accumulation(self):
-        return self.__dict__.get("_grad_accumulation")
-
-    @grad_accumulation.setter
-    def grad_accumulation(self, v):
-        self.__dict__["_grad_accumulation"] = check_grad_accumulation(v)
-
-    @property
-    def ema_decay(self):
-        return self.__dict__.get("_ema_decay")
-
-    @ema_decay.setter
-    def ema_decay(self, v):
-        self.__dict__["_ema_decay"] = check_ema_decay(v)
-
-    @property
-    def ema_warmup(self):
-        return self.__dict__.get("_ema_warmup", False)
-
-    @ema_warmup.setter
-    def ema_warmup(self, v):
-        self.__dict__["_ema_warmup"] = check_ema_flag("ema_warmup", v)
-
-    @property
-    def ema_eval(self):
-        return self.__dict__.get("_ema_eval", True)
-
-    @ema_eval.setter
-    def ema_eval(self, v):
-        self.__dict__["_ema_eval"] = check_ema_flag("ema_eval", v)
+    max_grad_norm = _Checked(check_max_grad_norm)
+    grad_norm_type = _Checked(check_grad_norm_type, 2.0)
+    loss_scale = _Checked(as_loss_scaler)   # the optimizer's mauv.amp.LossScaler, or None
+    grad_accumulation = _Checked(check_grad_accumulation)
+    ema_decay = _Checked(check_ema_decay)
+    ema_warmup = _Checked(functools.partial(check_ema_flag, "ema_warmup"), False)
+    ema_eval = _Checked(functools.partial(check_ema_flag, "ema_eval"), True)
 
     def accumulating(self):
         """Gradient accumulation is on (K > 1), or a window opened under it is still open."""
@@ -363,8 +381,8 @@ class FusedAdam(torch.optim.Optimizer):
         changed, no host synchronisation."""
         want = (self.max_grad_norm or 0.0, _kind(self.grad_norm_type))
         if self._gate_clip != want:
-            gate[G_MAX_NORM:G_MAX_NORM + 1].view(torch.float32).fill_(want[0])
-            gate[G_NORM_KIND:G_NORM_KIND + 1].fill_(want[1])
+            word(gate, G_MAX_NORM, fp32=True).fill_(want[0])
+            word(gate, G_NORM_KIND).fill_(want[1])
             self._gate_clip = want
 
     def scan_gated(self, gate, flat=None):
@@ -379,8 +397,7 @@ class FusedAdam(torch.optim.Optimizer):
             rows = _span_rows([p.grad for p, _ in self._gate_live])
         spans, ws = self._norm_plan.get(rows, gate.device)
         ops.grad_norm(spans, _kind(self.grad_norm_type), ws,
-                      gate[G_GRAD_NORM:G_GRAD_NORM + 1].view(torch.float32),
-                      gate[G_NONFINITE:G_NONFINITE + 1])
+                      word(gate, G_GRAD_NORM, fp32=True), word(gate, G_NONFINITE))
 
     @staticmethod
     def _check_group(group):
@@ -413,128 +430,22 @@ class FusedAdam(torch.optim.Optimizer):
         """One group, amsgrad / maximize / decoupled off: the mauv_adam_step entry points."""
         return len(self.param_groups) == 1 and _flags(self.param_groups[0]) == 0
 
-    def _table(self, gi, live):
-        key = tuple((p.data_ptr(), p.grad.data_ptr(), self.state[p]["exp_avg"].data_ptr(),
-                     self.state[p]["exp_avg_sq"].data_ptr()) for p in live)
-        cached = self._tables.get(gi)
-        if cached is not None and cached[0] == key:
-            return cached[1]
-        rows = np.zeros((len(live), 5), dtype=np.int64)
-        for i, p in enumerate(live):
-            st = self.state[p]
-            rows[i] = (p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(),
-                       st["exp_avg_sq"].data_ptr(), p.numel())
-        tab = torch.from_numpy(rows).to(live[0].device)
-        self._tables[gi] = (key, tab)
-        return tab
-
     def _layout(self, pairs):
         """What an all-groups table depends on besides the pointers: each row's group and every
         group's option flags (amsgrad adds a column)."""
         return tuple(gi for _, gi in pairs), tuple(_flags(g) for g in self.param_groups)
 
-    def _table_ex(self, key, pairs):
-        """(device table, launches) over ``pairs`` = [(parameter, group index)] in group order.
-        A launch is (first row, rows, its group indices): at most MAX_GROUPS groups each, a row's
-        group column counting within its launch."""
-        ams = [bool(g["amsgrad"]) for g in self.param_groups]
-        rows = np.zeros((len(pairs), 7), dtype=np.int64)
-        chunks = []
-        for i, (p, gi) in enumerate(pairs):
-            if not chunks or (gi != chunks[-1][2][-1] and len(chunks[-1][2]) == MAX_GROUPS):
-                chunks.append([i, 0, [gi]])
-            elif gi != chunks[-1][2][-1]:
-                chunks[-1][2].append(gi)
-            chunks[-1][1] += 1
-            st = self.state[p]
-            rows[i] = (p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(),
-                       st["exp_avg_sq"].data_ptr(),
-                       st["max_exp_avg_sq"].data_ptr() if ams[gi] else 0, p.numel(),
-                       len(chunks[-1][2]) - 1)
-        # with the weight EMA on, the rows' shadow pointers travel in a table of their own
-        sh = None
-        if self.ema_decay is not None:
-            sh = np.array([self.state[p]["ema"].data_ptr() for p, _ in pairs], dtype=np.int64)
-        ident = (rows.tobytes(), tuple((a, b, tuple(c)) for a, b, c in chunks),
-                 None if sh is None else sh.tobytes())
-        cached = self._tables.get(key)
-        if cached is not None and cached[0] == ident:
-            return cached[1]
-        dev = pairs[0][0].device
-        tab = (torch.from_numpy(rows).to(dev), ident[1],
-               None if sh is None else torch.from_numpy(sh).to(dev))
-        self._tables[key] = (ident, tab)
-        return tab
+    def _count(self, p):
+        """The parameter's step count on the host (0 before its first step)."""
+        return int(self.state[p]["step"].item()) if "step" in self.state.get(p, ()) else 0
 
-    def _launch_ex(self, tab, t, gate, scaler=None, accum=None, ema=None):
-        """mauv_adam_step_ex over every launch of ``tab``; the groups' current lr, betas, eps,
-        weight_decay and flags travel by value.  ``scaler``: the device MauvLossScale pointer of
-        a gated step with loss scaling (mauv_adam_step_ex_scaled; one launch).  ``accum``: the
-        device MauvAccum pointer of a gated step that closes an accumulation window
-        (mauv_adam_step_ex_accum, with or without a scaler; one launch).  ``ema``: the device
-        MauvEma pointer of a gated step with the weight EMA (mauv_adam_step_ex_ema, with or
-        without either of the others; one launch)."""
-        table, chunks, shadows = tab
-        assert (scaler is None and accum is None and ema is None) or \
-            (gate is not None and len(chunks) == 1)
-        assert ema is None or shadows is not None
-        for r0, n, gis in chunks:
-            arr = (MauvAdamGroup * len(gis))()
-            for a, gi in zip(arr, gis):
-                g = self.param_groups[gi]
-                a.lr, a.eps, a.weight_decay = g["lr"], g["eps"], g["weight_decay"]
-                (a.beta1, a.beta2), a.flags = g["betas"], _flags(g)
-            if ema is not None:
-                check(lib.mauv_adam_step_ex_ema(table.data_ptr() + 56 * r0, n,
-                                                ctypes.addressof(arr), len(gis), gate, scaler,
-                                                accum, shadows.data_ptr() + 8 * r0, ema,
-                                                ops.stream()), "adam_step_ex_ema")
-                continue
-            if accum is not None:
-                check(lib.mauv_adam_step_ex_accum(table.data_ptr() + 56 * r0, n,
-                                                  ctypes.addressof(arr), len(gis), gate, scaler,
-                                                  accum, ops.stream()), "adam_step_ex_accum")
-                continue
-            if scaler is not None:
-                check(lib.mauv_adam_step_ex_scaled(table.data_ptr() + 56 * r0, n,
-                                                   ctypes.addressof(arr), len(gis), gate, scaler,
-                                                   ops.stream()), "adam_step_ex_scaled")
-                continue
-            check(lib.mauv_adam_step_ex(table.data_ptr() + 56 * r0, n, ctypes.addressof(arr),
-                                        len(gis), t, gate, ops.stream()), "adam_step_ex")
+    def _shared_step_count(self, params):
+        """The sorted distinct step counts of ``params``: one entry when they share a count."""
+        return sorted({self._count(p) for p in params})
 
-    def _fast_entry(self, gi, live):
-        """The cached (t, table, step buffer) of group ``gi`` (or of all groups, EX) if it is
-        still valid for ``live``."""
-        fast = self._fast.get(gi)
-        if fast is None:
-            return None
-        ptrs, gptrs, moments, state_id, t, tab, steps = fast[:7]
-        if state_id != id(self.state) or len(ptrs) != len(live):
-            return None
-        if [p.data_ptr() for p in live] != ptrs or [p.grad.data_ptr() for p in live] != gptrs:
-            return None
-        try:
-            for p, mom in zip(live, moments):
-                st = self.state[p]
-                if st["exp_avg"] is not mom[0] or st["exp_avg_sq"] is not mom[1]:
-                    return None
-                if len(mom) == 3 and st["max_exp_avg_sq"] is not mom[2]:
-                    return None
-            if len(fast) > 8:   # the shadows the all-groups table points at (None: EMA off)
-                if (fast[8] is None) != (self.ema_decay is None):
-                    return None
-                for p, sh in zip(live, fast[8] or ()):
-                    if self.state[p]["ema"] is not sh:
-                        return None
-        except KeyError:
-            return None
-        return fast
-
-    def _prepare(self, gi, group, live):
-        """Slow path: create / bump the per-parameter state, launch per shared step count."""
-        self._fast.pop(gi, None)
-        for p in live:
+    def _prepare(self, pairs):
+        """Check the parameters and create the per-parameter state they lack."""
+        for p, gi in pairs:
             if p.dtype != torch.float32 or not p.is_cuda or not p.is_contiguous() \
                     or p.grad.is_sparse:
                 raise TypeError("FusedAdam: dense contiguous fp32 ROCm parameters only")
@@ -543,55 +454,103 @@ class FusedAdam(torch.optim.Optimizer):
                 st["step"] = torch.tensor(0.0)
                 st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                 st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-            if group["amsgrad"] and "max_exp_avg_sq" not in st:
+            if self.param_groups[gi]["amsgrad"] and "max_exp_avg_sq" not in st:
                 st["max_exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
             if self.ema_decay is not None and "ema" not in st:
                 # the shadow starts from the parameter's current value (also one that joins later)
                 st["ema"] = p.detach().clone(memory_format=torch.preserve_format)
 
-    def _remember(self, gi, live, t, tab, layout=None):
-        # re-home the step counters as 0-dim views of one CPU tensor (still float tensors,
-        # torch.optim.Adam-compatible): the fast path bumps them in one op
-        buf = torch.full((len(live),), float(t))
+    def _build(self, pairs, t, layout, old):
+        """The _Plan over ``pairs`` = [(parameter, group index)] in group order at step count
+        ``t``: the device table (``old``'s when nothing it holds changed), and the step counters
+        re-homed as views of one CPU tensor, which ``advance`` bumps in one op."""
+        plan, ex = _Plan(), layout is not None
+        live = [p for p, _ in pairs]
+        ams = [bool(g["amsgrad"]) for g in self.param_groups]
+        rows = np.zeros((len(pairs), 7 if ex else 5), dtype=np.int64)
+        chunks, plan.moments = [], []
+        for i, (p, gi) in enumerate(pairs):
+            if not chunks or (gi != chunks[-1][2][-1] and len(chunks[-1][2]) == MAX_GROUPS):
+                chunks.append([i, 0, [gi]])
+            elif gi != chunks[-1][2][-1]:
+                chunks[-1][2].append(gi)
+            chunks[-1][1] += 1
+            st = self.state[p]
+            mom = (st["exp_avg"], st["exp_avg_sq"]) + \
+                ((st["max_exp_avg_sq"],) if ams[gi] else ())
+            plan.moments.append(mom)
+            ptrs = (p.data_ptr(), p.grad.data_ptr(), mom[0].data_ptr(), mom[1].data_ptr())
+            rows[i] = ptrs + ((mom[2].data_ptr() if ams[gi] else 0, p.numel(),
+                               len(chunks[-1][2]) - 1) if ex else (p.numel(),))
+        plan.ptrs, plan.gptrs = rows[:, 0].tolist(), rows[:, 1].tolist()
+        plan.chunks = tuple((a, b, tuple(c)) for a, b, c in chunks) if ex else None
+        # with the weight EMA on, the rows' shadow pointers travel in a table of their own
+        plan.shadows = sh = None
+        if ex and self.ema_decay is not None:
+            plan.shadows = [self.state[p]["ema"] for p in live]
+            sh = np.array([e.data_ptr() for e in plan.shadows], dtype=np.int64)
+        plan.ident = (rows.tobytes(), plan.chunks, None if sh is None else sh.tobytes())
+        if old is not None and old.ident == plan.ident:
+            plan.table, plan.shadow_table = old.table, old.shadow_table
+        else:
+            dev = live[0].device
+            plan.table = torch.from_numpy(rows).to(dev)
+            plan.shadow_table = None if sh is None else torch.from_numpy(sh).to(dev)
+        plan.steps = torch.full((len(live),), float(t))
         for i, p in enumerate(live):
-            self.state[p]["step"] = buf[i]
-        moments = [(self.state[p]["exp_avg"], self.state[p]["exp_avg_sq"]) for p in live]
-        if layout is not None:   # every moment tensor the table points at, max_exp_avg_sq too
-            ams = [bool(g["amsgrad"]) for g in self.param_groups]
-            moments = [mom + (self.state[p]["max_exp_avg_sq"],) if ams[row_group] else mom
-                       for p, row_group, mom in zip(live, layout[0], moments)]
-        self._fast[gi] = ([p.data_ptr() for p in live], [p.grad.data_ptr() for p in live],
-                          moments, id(self.state), t, tab, buf) + \
-            (() if layout is None else
-             (layout, None if self.ema_decay is None else [self.state[p]["ema"] for p in live]))
+            self.state[p]["step"] = plan.steps[i]
+        plan.state_id, plan.t, plan.layout = id(self.state), t, layout
+        return plan
 
-    def _step_ex(self):
-        """The ungated step of anything but one plain group: every group with live parameters
-        in one launch (per shared step count, MAX_GROUPS groups per launch)."""
-        pairs = [(p, gi) for gi, g in enumerate(self.param_groups) for p in g["params"]
-                 if p.grad is not None]
-        if not pairs:
+    def _replan(self, key, by_count):
+        """The slow path of every route: the plans of ``by_count`` = {step count: pairs} under
+        ``key`` (0: one plain group, 5-column rows; EX: all groups).  One shared count is cached in
+        ``_fast[key]`` for the next step; several are kept by position in ``_split[key]``, which
+        only saves rebuilding their device tables.  Every other cached plan is dropped: its step
+        buffer may no longer be what the parameters' counters are views of."""
+        old = [self._fast[key]] if key in self._fast else self._split.get(key, [])
+        self._fast.clear()
+        self._split.clear()
+        for pairs in by_count.values():
+            self._prepare(pairs)
+        plans = [self._build(pairs, t, None if key == 0 else self._layout(pairs),
+                             old[i] if i < len(old) else None)
+                 for i, (t, pairs) in enumerate(by_count.items())]
+        if len(plans) == 1:
+            self._fast[key] = plans[0]
+        else:
+            self._split[key] = plans
+        return plans
+
+    def _launch(self, plan, gate=None, scaler=None, accum=None, ema=None):
+        """The Adam launch of ``plan`` at its step count, or (``gate``: the device MauvStepGate
+        pointer) gated, with the device MauvLossScale / MauvAccum / MauvEma pointers of whatever
+        is on.  The groups' current lr, betas, eps, weight_decay and flags travel by value."""
+        if plan.layout is None:
+            g = self.param_groups[0]
+            args = (plan.table.data_ptr(), len(plan.ptrs), g["lr"], *g["betas"], g["eps"],
+                    g["weight_decay"])
+            if gate is None:
+                check(lib.mauv_adam_step(*args, plan.t, ops.stream()), "adam_step")
+            else:
+                check(lib.mauv_adam_step_gated(*args, gate, ops.stream()), "adam_step_gated")
             return
-        live, layout = [p for p, _ in pairs], self._layout(pairs)
-        fast = self._fast_entry(EX, live)
-        if fast is not None and fast[7] == layout:
-            t = fast[4] + 1
-            fast[6].add_(1.0)   # every live parameter's state["step"] is a view of it
-            self._launch_ex(fast[5], t, None)
-            self._fast[EX] = fast[:4] + (t,) + fast[5:]
-            return
-        self._fast.pop(EX, None)
-        for gi, group in enumerate(self.param_groups):
-            self._prepare(EX, group, [p for p, g in pairs if g == gi])
-        steps = {}
-        for p, gi in pairs:
-            self.state[p]["step"] += 1
-            steps.setdefault(int(self.state[p]["step"].item()), []).append((p, gi))
-        for t, ps in steps.items():
-            tab = self._table_ex((EX, t) if len(steps) > 1 else EX, ps)
-            self._launch_ex(tab, t, None)
-            if len(steps) == 1:
-                self._remember(EX, live, t, tab, layout)
+        assert gate is None or len(plan.chunks) == 1   # gate() takes at most MAX_GROUPS groups
+        assert ema is None or plan.shadow_table is not None
+        for r0, n, gis in plan.chunks:
+            arr = (MauvAdamGroup * len(gis))()
+            for a, gi in zip(arr, gis):
+                g = self.param_groups[gi]
+                a.lr, a.eps, a.weight_decay = g["lr"], g["eps"], g["weight_decay"]
+                (a.beta1, a.beta2), a.flags = g["betas"], _flags(g)
+            args = (plan.table.data_ptr() + 56 * r0, n, ctypes.addressof(arr), len(gis))
+            if gate is None:
+                check(lib.mauv_adam_step_ex(*args, plan.t, None, ops.stream()), "adam_step_ex")
+            else:
+                check(lib.mauv_adam_step_ex_ema(
+                    *args, gate, scaler, accum,
+                    None if ema is None else plan.shadow_table.data_ptr() + 8 * r0, ema,
+                    ops.stream()), "adam_step_ex_ema")
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -634,40 +593,27 @@ class FusedAdam(torch.optim.Optimizer):
         self._ema_pushed = False
 
     def _step_adam(self):
-        """The Adam launches of the ungated step."""
-        if not self._simple():
-            self._step_ex()
+        """The Adam launches of the ungated step: one plain group through mauv_adam_step, anything
+        else through mauv_adam_step_ex, every group with live parameters in one launch (per
+        shared step count, MAX_GROUPS groups per launch)."""
+        pairs = [(p, gi) for gi, g in enumerate(self.param_groups) for p in g["params"]
+                 if p.grad is not None]
+        if not pairs:
             return
-        for gi, group in enumerate(self.param_groups):
-            live = [p for p in group["params"] if p.grad is not None]
-            if not live:
-                continue
-            b1, b2 = group["betas"]
-            fast = self._fast_entry(gi, live)
-            if fast is not None:
-                ptrs, gptrs, moments, sid, t, tab, steps = fast
-                t += 1
-                steps.add_(1.0)   # every live parameter's state["step"] is a view of it
-                check(lib.mauv_adam_step(tab.data_ptr(), len(live), group["lr"], b1, b2,
-                                         group["eps"], group["weight_decay"], t,
-                                         ops.stream()), "adam_step")
-                self._fast[gi] = (ptrs, gptrs, moments, sid, t, tab, steps)
-                continue
-            self._prepare(gi, group, live)
-            for p in live:
-                self.state[p]["step"] += 1
-            # one bias-correction step per group (params of a group step together; a param that
-            # missed steps because its grad was None keeps its own count like torch — split it)
-            steps = {}
-            for p in live:
-                steps.setdefault(int(self.state[p]["step"].item()), []).append(p)
-            for t, ps in steps.items():
-                tab = self._table((gi, t) if len(steps) > 1 else gi, ps)
-                check(lib.mauv_adam_step(tab.data_ptr(), len(ps), group["lr"], b1, b2,
-                                         group["eps"], group["weight_decay"], t,
-                                         ops.stream()), "adam_step")
-                if len(steps) == 1:
-                    self._remember(gi, ps, t, tab)
+        key = 0 if self._simple() else EX
+        plan = self._fast.get(key)
+        if plan is not None and plan.valid_for(self, [p for p, _ in pairs],
+                                               None if key == 0 else self._layout(pairs)):
+            plan.advance()
+            self._launch(plan)
+            return
+        # one bias-correction step per launch (a param that missed steps because its grad was
+        # None keeps its own count like torch — split it)
+        by_count = {}
+        for p, gi in pairs:
+            by_count.setdefault(self._count(p) + 1, []).append((p, gi))
+        for plan in self._replan(key, by_count):
+            self._launch(plan)
 
     def _step_scaled(self):
         """``step()`` with a loss scaler: the gated step on a gate of this optimizer's own over
@@ -691,25 +637,28 @@ class FusedAdam(torch.optim.Optimizer):
             all(a is b and i == j for (a, i), (b, j) in zip(self._gate_live, pairs))
         if not same:
             self._sync_gate()
-            counts = {int(self.state[p]["step"].item()) if "step" in self.state.get(p, ()) else 0
-                      for p, _ in pairs}
+            counts = self._shared_step_count(p for p, _ in pairs)
             if len(counts) != 1:
                 raise ValueError("FusedAdam: loss scaling steps through the device-gated form, "
                                  "which needs one step count for all parameters "
-                                 f"(found {sorted(counts)})")
-            g = torch.zeros(GATE_WORDS, dtype=torch.int32)
-            g[G_STEP] = counts.pop()
-            self._gate = g.to(dev)
-            self._gate_dirty = False
-            self._gate_clip = (0.0, 0)
+                                 f"(found {counts})")
+            self._new_gate(dev, counts[0], 0)
             self._gate_params = None
             self._gate_live = pairs
         gate = self._gate
-        gate[G_OK_LOSS:G_OK_LOSS + 1].fill_(1)
+        word(gate, G_OK_LOSS).fill_(1)
         self.scan_gated(gate)
         self._step_gated(gate)
 
     # ---- the device-gated form ---------------------------------------------------------------
+    def _new_gate(self, device, step, poisoned):
+        """A fresh device MauvStepGate at Adam step count ``step``."""
+        g = torch.zeros(GATE_WORDS, dtype=torch.int32)
+        g[G_STEP], g[G_POISONED] = step, poisoned
+        self._gate = g.to(device)
+        self._gate_dirty = False
+        self._gate_clip = (0.0, 0)
+
     def gate(self, params, device):
         """The device MauvStepGate for a training loop over ``params`` (the model's trainable
         parameters), or None when the gated form does not apply: 1 to 8 parameter groups whose
@@ -728,8 +677,7 @@ class FusedAdam(torch.optim.Optimizer):
         if len(gp) != len(params) or {id(p) for p in gp} != {id(p) for p in params}:
             return None
         if self._gate is None or self._gate.device != torch.device(device):
-            counts = {int(self.state[p]["step"].item()) if "step" in self.state.get(p, ()) else 0
-                      for p in gp}
+            counts = self._shared_step_count(gp)
             if len(counts) != 1:
                 return None
             # the gate takes a skipped batch's gradients back out by zeroing a clean arena, so it
@@ -745,12 +693,7 @@ class FusedAdam(torch.optim.Optimizer):
                     poisoned = 1
                 elif bool((top != 0).any()):
                     return None
-            g = torch.zeros(GATE_WORDS, dtype=torch.int32)
-            g[G_STEP] = counts.pop()
-            g[G_POISONED] = poisoned
-            self._gate = g.to(device)
-            self._gate_dirty = False
-            self._gate_clip = (0.0, 0)
+            self._new_gate(device, counts[0], poisoned)
         self._gate_params = params
         self._gate_live = pairs
         return self._gate
@@ -804,45 +747,19 @@ class FusedAdam(torch.optim.Optimizer):
         ema_on = self.ema_decay is not None
         # with a loss scaler, an accumulation window or the weight EMA every layout takes the
         # all-groups entry: one plain group there is adam_elem, the simple kernel's element
-        simple = self._simple() and ls is None and accum is None and not ema_on
-        if simple:
-            group = self.param_groups[0]
-            b1, b2 = group["betas"]
-            fast = self._fast_entry(0, live)
-            if fast is None:
-                self._fast.pop(EX, None)   # (its step buffer is re-homed below)
-                self._prepare(0, group, live)
-                tab = self._table(0, live)
-                t = int(self._gate_step_host())
-                self._remember(0, live, t, tab)
-                fast = self._fast[0]
-        else:
-            layout = self._layout(pairs)
-            fast = self._fast_entry(EX, live)
-            if fast is None or fast[7] != layout:
-                self._fast.pop(EX, None)
-                self._fast.pop(0, None)    # (its step buffer is re-homed below)
-                for gi, group in enumerate(self.param_groups):
-                    self._prepare(EX, group, [p for p, g in pairs if g == gi])
-                tab = self._table_ex(EX, pairs)
-                assert len(tab[1]) == 1   # gate() takes at most MAX_GROUPS groups
-                t = int(self._gate_step_host())
-                self._remember(EX, live, t, tab, layout)
-                fast = self._fast[EX]
-        tab = fast[5]
+        key = 0 if self._simple() and ls is None and accum is None and not ema_on else EX
+        layout = None if key == 0 else self._layout(pairs)
+        plan = self._fast.get(key)
+        if plan is None or not plan.valid_for(self, live, layout):
+            plan, = self._replan(key, {self._gate_step_host(): pairs})
         self._write_gate_clip(gate)   # (the caller's scan_gated wrote them already when on)
-        if simple:
-            check(lib.mauv_adam_step_gated(tab.data_ptr(), len(live), group["lr"], b1, b2,
-                                           group["eps"], group["weight_decay"], gate.data_ptr(),
-                                           ops.stream()), "adam_step_gated")
-        else:
-            self._launch_ex(tab, 0, gate.data_ptr(),
-                            None if ls is None else ls.device_state(gate.device).data_ptr(),
-                            None if accum is None else accum.data_ptr(),
-                            self._ema_state(gate.device).data_ptr() if ema_on else None)
-            self._ema_dirty = self._ema_dirty or ema_on
+        self._launch(plan, gate.data_ptr(),
+                     None if ls is None else ls.device_state(gate.device).data_ptr(),
+                     None if accum is None else accum.data_ptr(),
+                     self._ema_state(gate.device).data_ptr() if ema_on else None)
+        self._ema_dirty = self._ema_dirty or ema_on
         self.last_grad_norm = None if self.max_grad_norm is None else \
-            gate[G_GRAD_NORM:G_GRAD_NORM + 1].view(torch.float32).clone()[0]
+            word(gate, G_GRAD_NORM, fp32=True).clone()[0]
         self._gate_dirty = True
 
     def _gate_step_host(self):
@@ -863,11 +780,11 @@ class FusedAdam(torch.optim.Optimizer):
             e = self._ema = torch.from_numpy(w).to(device)
             self._ema_opts, self._ema_pushed = opts, True
         if self._ema_opts != opts:
-            e[E_DECAY:E_DECAY + 1].view(torch.float32).fill_(opts[0])
-            e[E_WARMUP:E_WARMUP + 1].fill_(int(opts[1]))
+            word(e, E_DECAY, fp32=True).fill_(opts[0])
+            word(e, E_WARMUP).fill_(int(opts[1]))
             self._ema_opts = opts
         if not self._ema_pushed:
-            e[E_UPDATES:E_UPDATES + 1].fill_(self._ema_updates)
+            word(e, E_UPDATES).fill_(self._ema_updates)
             self._ema_pushed = True
         return e
 
@@ -946,10 +863,8 @@ class FusedAdam(torch.optim.Optimizer):
                 st = self.state.get(p)   # (a frozen parameter has none, and gets none here)
                 if st is not None and "step" in st:
                     st["step"].fill_(float(t))
-        for key in (0, EX):
-            fast = self._fast.get(key)
-            if fast is not None:
-                self._fast[key] = fast[:4] + (t,) + fast[5:]
+        for plan in self._fast.values():   # (_split plans are rebuilt from the state's counts
+            plan.t = t                     # on every step: their t is never read again)
         self._gate_dirty = False
 
     def state_dict(self):
@@ -972,8 +887,8 @@ class FusedAdam(torch.optim.Optimizer):
             for k, v in self.defaults.items():
                 group.setdefault(k, v)
             self._check_group(group)
-        self._tables.clear()
         self._fast.clear()
+        self._split.clear()
         self._gate = None
         self._gate_dirty = False
         self._ema_rows = None

@@ -352,11 +352,11 @@ def mc_train_step(model, inputs_tuple, labels, criterion, optimizer, num_mc, bat
     # the scale this batch's backward runs with (the step's decision may change it)
     used_scale = None if ls is None else ls.scale_tensor(loss.device).clone()[0]
     if gate is not None:
-        from .optim import G_OK_LOSS, G_NONFINITE, G_STEPPED, G_SCRATCH
+        from .optim import word, G_OK_LOSS, G_NONFINITE, G_STEPPED, G_SCRATCH
         accumulating = optimizer.accumulating()
         closing = optimizer.closes_window(close_window)
-        ok = gate[G_OK_LOSS:G_OK_LOSS + 1]
-        ok.copy_(_batch_finite(loss, inputs_tuple, gate[G_SCRATCH:G_SCRATCH + 1]))
+        ok = word(gate, G_OK_LOSS)
+        ok.copy_(_batch_finite(loss, inputs_tuple, word(gate, G_SCRATCH)))
         if hasattr(model, "all_ranks_device"):
             model.all_ranks_device(ok)
         if hasattr(model, "window_open"):   # DistributedMC exchanges the closing sums only
@@ -368,7 +368,7 @@ def mc_train_step(model, inputs_tuple, labels, criterion, optimizer, num_mc, bat
             if optimizer.max_grad_norm is not None:
                 _scan_grad_norm(model, optimizer, gate)
             else:
-                _count_nonfinite(model, gate[G_NONFINITE:G_NONFINITE + 1])
+                _count_nonfinite(model, word(gate, G_NONFINITE))
         if accumulating:
             optimizer.step_gated(gate, close=closing)
         else:

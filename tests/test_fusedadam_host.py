@@ -125,3 +125,40 @@ def test_adam_step_ex_argument_errors_need_no_device():
     for n, ng, step in ((0, 1, 1), (65536, 1, 1), (1, 0, 1), (1, 9, 1), (1, 1, 0)):
         assert lib.mauv_adam_step_ex(tab, n, grp, ng, step, None, None) == -1, (n, ng, step)
         assert b"adam_step_ex" in lib.mauv_last_error()
+
+
+def test_gated_entries_argument_errors_start_with_their_own_name():
+    """Every gated all-groups entry refuses n = 0, n = 65536, 0 or 9 groups, a null table, null
+    groups and a null gate before any launch, with ERR_ARG and a message that starts with the
+    entry's own name — also with every optional pointer NULL, where the entry computes exactly
+    what the one before it does."""
+    from mauv._lib import lib, MauvAdamGroup, MauvLossScale, MauvAccum, MauvEma
+    arr = (MauvAdamGroup * 8)()
+    table = (ctypes.c_longlong * 7)()
+    gate = (ctypes.c_int * 16)()
+    shadows = (ctypes.c_void_p * 1)()
+    ls, acc, ema = MauvLossScale(scale=2.0), MauvAccum(), MauvEma(decay=0.9)
+    tab, grp, gp, lp, ap, sp, ep = (ctypes.addressof(x)
+                                    for x in (table, arr, gate, ls, acc, shadows, ema))
+    entries = {
+        "adam_step_ex": lambda t, n, g, ng, gt, on: lib.mauv_adam_step_ex(t, n, g, ng, 0, gt, None),
+        "adam_step_ex_scaled": lambda t, n, g, ng, gt, on: lib.mauv_adam_step_ex_scaled(
+            t, n, g, ng, gt, lp if on else None, None),
+        "adam_step_ex_accum": lambda t, n, g, ng, gt, on: lib.mauv_adam_step_ex_accum(
+            t, n, g, ng, gt, lp if on else None, ap if on else None, None),
+        "adam_step_ex_ema": lambda t, n, g, ng, gt, on: lib.mauv_adam_step_ex_ema(
+            t, n, g, ng, gt, lp if on else None, ap if on else None, sp if on else None,
+            ep if on else None, None),
+    }
+    cases = [(tab, 0, grp, 1, gp), (tab, 65536, grp, 1, gp), (tab, 1, grp, 0, gp),
+             (tab, 1, grp, 9, gp), (None, 1, grp, 1, gp), (tab, 1, None, 1, gp),
+             (tab, 1, grp, 1, None)]
+    for name, call in entries.items():
+        for case in cases:
+            if name == "adam_step_ex" and case[4] is None:
+                continue   # a null gate is this entry's ungated form (refused above at step 0)
+            for on in (True, False):
+                assert call(*case, on) == -1, (name, case[1], case[3], on)
+                msg = lib.mauv_last_error()
+                assert msg.startswith(name.encode() + b": "), (name, msg)
+    assert list(gate) == [0] * 16 and ls.scale == 2.0 and acc.windows == 0 and ema.updates == 0
